@@ -8,6 +8,12 @@ over RCCL, and prints ONE JSON line from rank 0.
 Weak scaling: per-GPU work is fixed at 128 seq x 1024 tok = 131072
 tokens/GPU/step, so N=8 reproduces the reference's global batch 1024
 (reference src/configs/openwebtext_xl.py; BASELINE.md 444K tok/s).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the
+result line; nothing else is measured. ``--dump-outputs DIR`` also writes
+what the last timed step computed (see ``_dump_outputs``) so two builds
+can be compared output for output. ``--full`` is reserved for secondary
+measurements; this benchmark has none today, so it changes nothing.
 """
 from __future__ import annotations
 
@@ -16,6 +22,7 @@ import json
 import os
 import time
 
+import numpy as np
 import torch
 
 from midgpt_amd.config import load_config
@@ -41,6 +48,34 @@ def _self_launch(n: int):
     raise SystemExit(subprocess.call(cmd))
 
 
+# weights written by --dump-outputs: a fixed seeded sample, 16 MB as fp32
+_DUMP_SAMPLE = 1 << 22
+
+
+def _dump_outputs(outdir: str, losses, sq, engine):
+    """Write the last timed step's results as float32 ``<name>.npy``:
+
+    loss          (g_accum,) the loss each microbatch's forward returned
+    grad_sq_sum   (1,) what ``engine.step`` returned (pre-clip sum of squares)
+    weights       the working weights the step left behind, all of them if
+                  they fit in the sample size, else a seeded sample in flat
+                  parameter order
+    """
+    os.makedirs(outdir, exist_ok=True)
+    flat = engine.flat_w[:engine.total]
+    if engine.total > _DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(4321)
+        idx = torch.randint(0, engine.total, (_DUMP_SAMPLE,), generator=g)
+        flat = flat[idx.sort().values.to(flat.device)]
+    out = {
+        "loss": torch.stack([l.detach().float().reshape(()) for l in losses]),
+        "grad_sq_sum": sq.detach().float().reshape(1),
+        "weights": flat.detach().float(),
+    }
+    for name, t in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -60,7 +95,14 @@ def main():
                         "microbatch for every config incl. 7B@4096)")
     p.add_argument("--no-remat", action="store_true",
                    help="force remat OFF even at seq > 1024 (memory permitting)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one "
+                        "computed as DIR/<name>.npy (rank 0)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (none today)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
 
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) <= 1:
         _self_launch(args.gpus)  # re-exec under torchrun; does not return
@@ -109,12 +151,14 @@ def main():
                               decay_steps=config.lr_decay_steps,
                               min_lr=config.min_lr)
         x, y = batches[it % len(batches)]
+        losses = []
         for g in range(g_accum):
             loss = model.loss(x[g], y[g])
             loss.backward()
             engine.microstep_end()
-        engine.step(lr, g_accum)
-        return loss
+            losses.append(loss)
+        sq = engine.step(lr, g_accum)
+        return losses, sq
 
     for w in range(args.warmup):
         one_step(w)
@@ -124,11 +168,15 @@ def main():
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(args.steps):
-        loss = one_step(args.warmup + it)
+        losses, sq = one_step(args.warmup + it)
     pdist.barrier()
     if device.type == "cuda":
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    loss = losses[-1]
+
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, losses, sq, engine)
 
     # MAX over ranks
     t = torch.tensor([elapsed], dtype=torch.float64)

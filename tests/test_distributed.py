@@ -22,18 +22,21 @@ def _make_batch():
 
 
 def _train_local(zero: bool, steps=3):
-    """Single-process reference: full batch of 8."""
+    """Single-process reference: full batch of 8. Also returns, per
+    weight, the smallest |gradient| any step saw."""
     from midgpt_amd.models.gpt import GPT
     from midgpt_amd.parallel.engine import ShardedAdamW
     torch.manual_seed(0)
     model = GPT(TINY)
     engine = ShardedAdamW(model, compute_dtype=torch.float32, zero=zero)
     x, y = _make_batch()
+    min_g = torch.full_like(engine.master, float("inf"))
     for _ in range(steps):
         model.loss(x, y).backward()
         engine.microstep_end()
+        min_g = torch.minimum(min_g, engine.g32.abs())
         engine.step(1e-3)
-    return engine.master.clone()
+    return engine.master.clone(), min_g
 
 
 def _worker(rank, world, init_file, zero, out_q, steps=3):
@@ -79,10 +82,20 @@ def test_two_rank_matches_single_process(zero, tmp_path):
     for p in procs:
         p.join(timeout=120)
         assert p.exitcode == 0
-    ref = _train_local(zero=False)
+    ref, min_g = _train_local(zero=False)
+    # Adam moves a weight by lr*g/(|g|+eps), eps=1e-8. One batch of 8 and
+    # two of 4 sum in a different order, which shifts g by ~1e-8 in fp32;
+    # where |g| itself is that small the update changes by a visible part
+    # of lr and 2e-5 cannot hold on every CPU. Those few weights (|g| <
+    # 1e-6 in some step: the shift is <1% of g above that) are only held to
+    # the distance Adam can move them at all, 3 steps of at most 2*lr.
+    tiny = min_g < 1e-6
+    assert tiny.sum() <= 0.001 * tiny.numel(), tiny.sum()
+    atol = torch.where(tiny, 3 * 2e-3, 2e-5)
+    assert torch.equal(results[0], results[1])  # replicas stay in lockstep
     for r, full in results.items():
-        assert torch.allclose(full, ref[:full.numel()], atol=2e-5), \
-            (r, (full - ref[:full.numel()]).abs().max())
+        err = (full - ref[:full.numel()]).abs()
+        assert (err <= atol[:full.numel()]).all(), (r, err.max())
 
 
 def _ckpt_worker(rank, world, init_file, rundir, out_q):

@@ -7,6 +7,10 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
+# These are CPU-tier runs (fp32 compute, which the HIP kernels refuse): on a
+# machine with a GPU the child processes must not see it.
+CPU_ENV = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+
 TINY_CFG = '''
 from midgpt_amd.config import ExperimentConfig, GPTConfig
 config = ExperimentConfig(
@@ -30,7 +34,8 @@ def test_launch_and_sample_cli(tmp_path):
         r = subprocess.run(
             [sys.executable, "launch.py", "--config=_tiny_ci",
              f"--rundir={rundir}"],
-            cwd=REPO, capture_output=True, text=True, timeout=300)
+            cwd=REPO, env=CPU_ENV, capture_output=True, text=True,
+            timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         # rundir contract: config.json + a committed checkpoint
         cfg = json.load(open(os.path.join(rundir, "config.json")))
@@ -41,7 +46,8 @@ def test_launch_and_sample_cli(tmp_path):
         r2 = subprocess.run(
             [sys.executable, "launch.py", "--config=_tiny_ci",
              f"--rundir={rundir}"],
-            cwd=REPO, capture_output=True, text=True, timeout=300)
+            cwd=REPO, env=CPU_ENV, capture_output=True, text=True,
+            timeout=300)
         assert r2.returncode == 0, r2.stderr[-2000:]
         assert "resumed from step" in (r2.stdout + r2.stderr)
         # sample.py needs a tokenizer: char meta or tiktoken (offline) —
@@ -61,19 +67,24 @@ def test_launch_and_sample_cli(tmp_path):
             [sys.executable, "sample.py", f"--ckpt_dir={rundir}",
              "--start=ab", "--num_samples=1", "--max_new_tokens=8",
              "--seed=0"],
-            cwd=REPO, capture_output=True, text=True, timeout=300)
+            cwd=REPO, env=CPU_ENV, capture_output=True, text=True,
+            timeout=300)
         assert r3.returncode == 0, r3.stderr[-2000:]
         assert "---------------" in r3.stdout
     finally:
         os.remove(cfg_path)
 
 
-def test_serve_endpoint(tmp_path):
+def test_serve_endpoint(tmp_path, monkeypatch):
     """serve.py: health + generation over a tiny trained rundir."""
     import json
     import pickle
 
     import numpy as np
+    import torch
+
+    # fp32 CPU-tier config: train() must pick the CPU even beside a GPU
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
 
     from midgpt_amd.train import train
     from tests.test_model_train import tiny_config

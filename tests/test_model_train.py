@@ -249,8 +249,10 @@ def test_evaluate_reads_requested_split(tmp_path):
     assert evaluate(m, bl, "val", 2, dev, n_batches=3) == pytest.approx(11.0)
 
 
-def test_train_entrypoint_runs(tmp_path):
+def test_train_entrypoint_runs(tmp_path, monkeypatch):
     from midgpt_amd.train import train
+    # fp32 CPU-tier config: train() must pick the CPU even beside a GPU
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     cfg = tiny_config(tmp_path, max_steps=3, eval_interval=2, debug=True)
     train(cfg)
 

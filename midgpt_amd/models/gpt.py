@@ -87,14 +87,17 @@ class CausalSelfAttention(nn.Module):
         qkv = self.c_attn(x).view(B, T, 3, self.n_head, self.head_dim)
         q, k, v = ops.qkv_prep(qkv, self.q_ln_weight, self.k_ln_weight,
                                sin[:T], cos[:T])
-        if self.dropout > 0.0 and self.training:
-            # Attention-matrix dropout requires materialized probabilities;
-            # only the shakespeare_char config uses it (reference
-            # src/model.py:78). Not a hot path.
+        if (self.dropout > 0.0 and self.training
+                and os.environ.get("MIDGPT_ATTN_DROPOUT_REF") == "1"):
+            # A/B only: the materialized O(T^2) path (torch softmax +
+            # F.dropout, differentiated by autograd).
             from midgpt_amd.ops import reference as refops
             o = refops.causal_attention(q, k, v, self.dropout, True)
         else:
-            o = ops.flash_attention(q, k, v)
+            # Attention-matrix dropout (reference src/model.py:78) runs
+            # inside the flash kernels, forward and backward.
+            o = ops.flash_attention(q, k, v,
+                                    self.dropout if self.training else 0.0)
         o = o.transpose(1, 2).reshape(B, T, D)
         return self.resid_dropout(self.c_proj(o))
 

@@ -194,11 +194,22 @@ def qkv_prep(qkv, q_ln_weight, k_ln_weight, sin, cos, eps: float = 1e-6):
 # Flash-style causal attention (reference src/model.py:71-79; plan K1/K2)
 # ----------------------------------------------------------------------------
 class _Attention(torch.autograd.Function):
+    """dropout_p > 0: attention-matrix dropout with the stateless Philox
+    keep-mask of csrc/philox.h, a pure function of (seed, b*H+h, q, k).
+    Nothing is stored: the backward (and an activation-remat replay)
+    regenerates the mask from the seed. The CPU branch applies the bit-exact
+    host mirror, so one seed gives one mask on CPU and on GPU. LSE is that of
+    the undropped softmax in both branches."""
+
     @staticmethod
-    def forward(ctx, q, k, v):
+    def forward(ctx, q, k, v, dropout_p=0.0, seed=0):
+        ctx.dropout_p, ctx.seed = dropout_p, seed
         if _use_hip(q):
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-            o, lse = _C.attn_fwd(q, k, v)
+            if dropout_p > 0.0:
+                o, lse = _C.attn_fwd_dropout(q, k, v, dropout_p, seed)
+            else:
+                o, lse = _C.attn_fwd(q, k, v)
         else:
             B, H, T, C = q.shape
             s = torch.matmul(q.float(), k.float().transpose(-1, -2)) / math.sqrt(C)
@@ -206,6 +217,8 @@ class _Attention(torch.autograd.Function):
             s = s.masked_fill(~mask, float("-inf"))
             lse = torch.logsumexp(s, dim=-1)  # (B,H,T) fp32
             a = torch.exp(s - lse[..., None])
+            if dropout_p > 0.0:
+                a = a * _cpu_dropout_scale(seed, B, H, T, dropout_p, a)
             o = torch.matmul(a.to(v.dtype), v)
         ctx.save_for_backward(q, k, v, o, lse)
         return o
@@ -213,8 +226,30 @@ class _Attention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
+        dropout_p = ctx.dropout_p
         if _use_hip(q):
-            dq, dk, dv = _C.attn_bwd(do.contiguous(), q, k, v, o, lse)
+            if dropout_p > 0.0:
+                dq, dk, dv = _C.attn_bwd_dropout(do.contiguous(), q, k, v, o, lse,
+                                                 dropout_p, ctx.seed)
+            else:
+                dq, dk, dv = _C.attn_bwd(do.contiguous(), q, k, v, o, lse)
+        elif dropout_p > 0.0:
+            B, H, T, C = q.shape
+            scale = 1.0 / math.sqrt(C)
+            s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
+            mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
+            s = s.masked_fill(~mask, float("-inf"))
+            p = torch.exp(s - lse[..., None])          # undropped P, fp32
+            z = _cpu_dropout_scale(ctx.seed, B, H, T, dropout_p, p)
+            dof = do.float()
+            dv = torch.matmul((p * z).transpose(-1, -2), dof)
+            dp = torch.matmul(dof, v.float().transpose(-1, -2)) * z
+            # rowsum(dO*O) = sum_j P_ij dP_ij also holds for the dropped O
+            delta = (dof * o.float()).sum(dim=-1, keepdim=True)
+            ds = p * (dp - delta)
+            dq = torch.matmul(ds, k.float()) * scale
+            dk = torch.matmul(ds.transpose(-1, -2), q.float()) * scale
+            dq, dk, dv = dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
         else:
             B, H, T, C = q.shape
             scale = 1.0 / math.sqrt(C)
@@ -230,12 +265,41 @@ class _Attention(torch.autograd.Function):
             dq = torch.matmul(ds, k.float()) * scale
             dk = torch.matmul(ds.transpose(-1, -2), q.float()) * scale
             dq, dk, dv = dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
-        return dq, dk, dv
+        return dq, dk, dv, None, None
 
 
-def flash_attention(q, k, v):
-    """Causal attention, q/k/v (B,H,T,C). Softmax scale 1/sqrt(C) in fp32."""
-    return _Attention.apply(q, k, v)
+def _cpu_dropout_scale(seed, B, H, T, p, like):
+    """Z = keep/(1-p) from the host mirror of the kernels' keep-mask."""
+    keep = ref.attn_dropout_keep(seed, B, H, T, p)
+    return keep.to(device=like.device, dtype=like.dtype) / (1.0 - p)
+
+
+def draw_dropout_seed() -> int:
+    """63-bit seed from torch's default CPU generator: no device sync,
+    reproducible under torch.manual_seed, replayed by torch.utils.checkpoint
+    (which preserves RNG state), and sequential draws give successive
+    layers different seeds."""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+
+
+def flash_attention(q, k, v, dropout_p: float = 0.0, seed: int | None = None):
+    """Causal attention, q/k/v (B,H,T,C). Softmax scale 1/sqrt(C) in fp32.
+
+    ``dropout_p > 0`` drops attention probabilities inside the kernels
+    (fwd + bwd) with a counter-based mask keyed by ``seed``; with
+    ``seed=None`` the seed is drawn by ``draw_dropout_seed``.
+    ``dropout_p == 0`` is exactly the undropped path."""
+    dropout_p = float(dropout_p)
+    if dropout_p == 0.0:
+        return _Attention.apply(q, k, v)
+    if not 0.0 < dropout_p < 1.0:
+        raise ValueError(f"flash_attention: dropout_p must be in [0, 1), got {dropout_p}")
+    if seed is None:
+        seed = draw_dropout_seed()
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if seed >= 1 << 63:  # the binding takes the same 64 bits as an int64
+        seed -= 1 << 64
+    return _Attention.apply(q, k, v, dropout_p, seed)
 
 
 # ----------------------------------------------------------------------------

@@ -19,6 +19,7 @@
 // (rowsum(dO*O)) runs first.
 #include "common.h"
 #include "mfma.h"
+#include "philox.h"
 
 // ---------------------------------------------------------------------------
 // LDS swizzles
@@ -132,18 +133,48 @@ DEVINL bf16x8_t read_tr_frag(const u16* lds, int row, int kbyte) {
 
 DEVINL float shfl32(float v, int src) { return __shfl(v, src, 32); }
 
+// dlayout_to_afrag (mfma.h) with a dropout keep mask: bit i of m8 clear
+// zeroes s[i]. The mask is applied to the packed bf16 pairs, so no second
+// fp32 copy of the 8 values is ever live.
+DEVINL bf16x8_t dlayout_to_afrag_keep(const float* s /*8 vals*/, uint32_t m8) {
+  unsigned x[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned mk = (((m8 >> (2 * i)) & 1u) ? 0x0000ffffu : 0u) |
+                        (((m8 >> (2 * i + 1)) & 1u) ? 0xffff0000u : 0u);
+    x[i] = pack_bf16(s[2 * i], s[2 * i + 1]) & mk;
+  }
+  {
+    auto r = __builtin_amdgcn_permlane32_swap(x[0], x[2], false, false);
+    x[0] = r[0]; x[2] = r[1];
+  }
+  {
+    auto r = __builtin_amdgcn_permlane32_swap(x[1], x[3], false, false);
+    x[1] = r[0]; x[3] = r[1];
+  }
+  union { unsigned u[4]; bf16x8_t v; } out;
+  out.u[0] = x[0]; out.u[1] = x[1]; out.u[2] = x[2]; out.u[3] = x[3];
+  return out.v;
+}
+
 // ===========================================================================
 // Forward. SPW strips per wave: with SPW=2 each wave owns MIRRORED strips
 // (w and NW*SPW-1-w), so causal work per wave is exactly equal and the
 // staging barriers park nobody (the measured 50% SQ_WAIT_ANY at SPW=1 came
 // from low-diagonal waves waiting on high-diagonal ones).
 // ===========================================================================
-template <int C, int NW, int SPW, int MINW>
+//
+// DROP: attention dropout (philox.h). m, lsum and the saved LSE come from
+// the UNDROPPED P; only the P fragments fed to the PV MFMA are masked, and
+// 1/(1-p) is folded into the epilogue's 1/lsum.
+template <int C, int NW, int SPW, int MINW, bool DROP = false>
 __global__ __launch_bounds__(NW * 64, MINW) void attn_fwd_kernel(const u16* __restrict__ q,
                                 const u16* __restrict__ k,
                                 const u16* __restrict__ v,
                                 u16* __restrict__ o, float* __restrict__ lse,
-                                int B, int H, int T) {
+                                int B, int H, int T,
+                                uint32_t seed_lo = 0, uint32_t seed_hi = 0,
+                                uint32_t drop_thr = 0, float inv_keep = 1.f) {
   constexpr int NCB = C / 32;   // 32-col c-blocks
   constexpr int NCH = C / 16;   // 16-deep mfma chunks
   constexpr int NSTRIP = NW * SPW;
@@ -251,6 +282,29 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_fwd_kernel(const u16* __re
 #pragma unroll
           for (int r = 0; r < 16; ++r) oacc[sp][cb][r] *= arow[r];
       }
+      if constexpr (DROP) {
+        // The mask groups four consecutive q at one k into one Philox
+        // call; here registers run along k at ONE q, but the four lanes of
+        // a quad hold q = 4g..4g+3 at the same 16 k. Lane j = lane&3 of
+        // the quad evaluates the calls of registers 4j..4j+3 (bit 4c+i of
+        // its mask = keep(q = 4g+i, k of reg 4j+c)); every lane then reads
+        // the four quad masks and picks its own q's bit.
+        const int j = lane & 3;
+        const uint32_t q4 = (uint32_t)myq >> 2;
+        uint32_t mine = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          mine |= attn_drop_keep4(seed_lo, seed_hi, (uint32_t)bh, q4,
+                                  (uint32_t)(k0 + c + 8 * j + 4 * (lane >> 5)),
+                                  drop_thr) << (4 * c);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const uint32_t mg = (uint32_t)__shfl((int)mine, g, 4);
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (!((mg >> (4 * c + j)) & 1u)) p[4 * g + c] = 0.f;
+        }
+      }
       // P -> bf16 A-fragments; PV
       bf16x8_t pf0 = dlayout_to_afrag(p);
       bf16x8_t pf1 = dlayout_to_afrag(p + 8);
@@ -275,7 +329,8 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_fwd_kernel(const u16* __re
   for (int sp = 0; sp < SPW; ++sp) {
     const int qw0 = q0 + 32 * strip[sp];
     const int myq = qw0 + (lane & 31);
-    const float rec = 1.f / lsum[sp];
+    float rec = 1.f / lsum[sp];
+    if constexpr (DROP) rec *= inv_keep;  // Z = keep/(1-p): scale applied once
     float rrow[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) rrow[r] = shfl32(rec, mfma_d_row(lane, r));
@@ -655,6 +710,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
 
 // ===========================================================================
 // delta = rowsum(dO * O) — one wave per row (prologue of backward)
+// Unchanged under dropout: with O_i = sum_j P_ij Z_ij V_j (Z = keep/(1-p)),
+// dO_i.O_i = sum_j P_ij Z_ij (dO_i.V_j) = sum_j P_ij dP_ij, dP = (dO V^T)oZ.
 // ===========================================================================
 __global__ void attn_delta_kernel(const u16* __restrict__ dO,
                                   const u16* __restrict__ O,
@@ -682,12 +739,19 @@ __global__ void attn_delta_kernel(const u16* __restrict__ dO,
 // stage-barrier-compute structure exposes). dK/dV accumulate in registers.
 // S and dS are recomputed from Q,K,LSE (standard flash recompute).
 // ===========================================================================
-template <int C, int NW, int ABLATE = 0, int MINW = 2>
+//
+// DROP (Z = keep/(1-p), philox.h): dV += (PoZ)^T dO, dP = (dO V^T)oZ,
+// dS = P o (dP - delta) * scale. Registers 4g..4g+3 are four consecutive q
+// (4-aligned) at this lane's k: one Philox call per register group. The
+// 1/(1-p) of dV is applied once, in the epilogue.
+template <int C, int NW, int ABLATE = 0, int MINW = 2, bool DROP = false>
 __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
     const u16* __restrict__ dO, const u16* __restrict__ q,
     const u16* __restrict__ k, const u16* __restrict__ v,
     const float* __restrict__ lse, const float* __restrict__ delta,
-    u16* __restrict__ dk, u16* __restrict__ dv, int B, int H, int T) {
+    u16* __restrict__ dk, u16* __restrict__ dv, int B, int H, int T,
+    uint32_t seed_lo = 0, uint32_t seed_hi = 0, uint32_t drop_thr = 0,
+    float inv_keep = 1.f) {
   constexpr int NCB = C / 32;
   constexpr int NCH = C / 16;
   constexpr int TILE = 4 * 32 * C;  // u16 elems per buffer set (Q,Qt,dO,dOt)
@@ -715,7 +779,10 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
   // measured -20% on dkv C=128 in a full-step profile despite removing
   // the 2-VGPR spill — the per-tile global loads add latency the spill
   // never cost); re-read only under the MINW=3 squeeze experiment.
-  constexpr bool KF_RES = (MINW <= 2);
+  // Under DROP at C=128 the keep mask and its select/scale code do not
+  // fit beside 32 VGPRs of resident K (the DROP=false kernel already sits
+  // at the 256 cap with 2 spills), so that variant re-reads K too.
+  constexpr bool KF_RES = (MINW <= 2) && !(DROP && C == 128);
   bf16x8_t kf[KF_RES ? NCH : 1];
   if (KF_RES) {
 #pragma unroll
@@ -767,6 +834,18 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
       const u16* ldsDOt = ldsDO + 32 * C;
       const float* lseb = ldsLse + buf * 32;
       const float* deltab = ldsDelta + buf * 32;
+      // DROP: bit r = keep(q of reg r, myk). Evaluated before the MFMA
+      // phase, while s/dp/p/ds are dead, and fenced so the Philox
+      // temporaries never overlap them (the kernel sits at the VGPR cap).
+      uint32_t keep = 0;
+      if constexpr (DROP) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          keep |= attn_drop_keep4(seed_lo, seed_hi, (uint32_t)bh,
+                                  (uint32_t)(qbase + 8 * g + 4 * (lane >> 5)) >> 2,
+                                  (uint32_t)myk, drop_thr) << (4 * g);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       // S = Q x K^T (D rows = q regs, cols = k lanes)
       f32x16 s = (f32x16)(0.f);
 #pragma unroll
@@ -788,7 +867,10 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
       }
       // dV += P^T x dO
       bf16x8_t pf0, pf1;
-      if (ABLATE == 4) {  // skip the permlane pack, keep p live
+      if constexpr (DROP) {
+        pf0 = dlayout_to_afrag_keep(p, keep);
+        pf1 = dlayout_to_afrag_keep(p + 8, keep >> 8);
+      } else if (ABLATE == 4) {  // skip the permlane pack, keep p live
         asm volatile("" :: "v"(p[0]), "v"(p[8]));
         pf0 = kf[0]; pf1 = kf[0];
       } else {
@@ -817,8 +899,11 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
       // dS = P * (dP - delta[q]) * scale; dK += dS^T x Q
       float ds[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r)
-        ds[r] = p[r] * (dp[r] - deltab[mfma_d_row(lane, r)]) * scale;
+      for (int r = 0; r < 16; ++r) {
+        float dpr = dp[r];
+        if constexpr (DROP) dpr = ((keep >> r) & 1u) ? dpr * inv_keep : 0.f;
+        ds[r] = p[r] * (dpr - deltab[mfma_d_row(lane, r)]) * scale;
+      }
       bf16x8_t df0, df1;
       if (ABLATE == 4) {
         asm volatile("" :: "v"(ds[0]), "v"(ds[8]));
@@ -866,8 +951,9 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = mfma_d_row(lane, r);
-        *(float*)((char*)ob + row * 128 + (((lane & 31) * 4) ^ ((row & 7) << 4))) =
-            acc[cb][r];
+        float a = acc[cb][r];
+        if constexpr (DROP) { if (which == 1) a *= inv_keep; }
+        *(float*)((char*)ob + row * 128 + (((lane & 31) * 4) ^ ((row & 7) << 4))) = a;
       }
       __builtin_amdgcn_s_waitcnt(0);
       const int row = lane & 31;
@@ -895,12 +981,16 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
 // see forward); iterates k tiles up to the max diagonal, DOUBLE-BUFFERED.
 // dQ accumulates in registers — no atomics.
 // ===========================================================================
-template <int C, int NW, int SPW, int MINW>
+// DROP: same dP = (dO V^T)oZ and dS as the dkv kernel; registers 4g..4g+3
+// are four consecutive q at this lane's k, one Philox call per group.
+template <int C, int NW, int SPW, int MINW, bool DROP = false>
 __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dq_kernel(
     const u16* __restrict__ dO, const u16* __restrict__ q,
     const u16* __restrict__ k, const u16* __restrict__ v,
     const float* __restrict__ lse, const float* __restrict__ delta,
-    u16* __restrict__ dq, int B, int H, int T) {
+    u16* __restrict__ dq, int B, int H, int T,
+    uint32_t seed_lo = 0, uint32_t seed_hi = 0, uint32_t drop_thr = 0,
+    float inv_keep = 1.f) {
   constexpr int NCB = C / 32;
   constexpr int NCH = C / 16;
   constexpr int NSTRIP = NW * SPW;
@@ -924,13 +1014,17 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dq_kernel(
   const u16* vg = v + (bh * T) * C;
   const u16* dog = dO + (bh * T) * C;
 
-  bf16x8_t qf[NCH];  // registers only for the last (busiest) strip
+  // Under DROP at C=128 the keep mask does not fit beside 32 VGPRs of
+  // resident Q (the DROP=false kernel uses 255 of 256), so that variant
+  // re-reads Q from global (L2-resident) like the non-last strips do.
+  constexpr bool QF_RES = !(DROP && C == 128);
+  bf16x8_t qf[QF_RES ? NCH : 1];  // registers only for the last (busiest) strip
   f32x16 dqacc[SPW][NCB];
   float mylse[SPW], mydelta[SPW];
 #pragma unroll
   for (int sp = 0; sp < SPW; ++sp) {
     const long myq = q0 + 32 * strip[sp] + (lane & 31);
-    if (sp == SPW - 1) {
+    if (QF_RES && sp == SPW - 1) {
       const u16* qrow = qg + myq * C;
 #pragma unroll
       for (int ch = 0; ch < NCH; ++ch)
@@ -971,13 +1065,25 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dq_kernel(
       if (k0 > qw0 + 31) continue;
       const u16* qrow = qg + (long)(qw0 + (lane & 31)) * C;
       const u16* dorow = dog + (long)(qw0 + (lane & 31)) * C;
+      // DROP: bit r = keep(q of reg r, kcol). Evaluated before the MFMA
+      // phase, while s/dp/ds are dead, and fenced so the Philox
+      // temporaries never overlap them (the kernel sits at the VGPR cap).
+      uint32_t keep = 0;
+      if constexpr (DROP) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          keep |= attn_drop_keep4(seed_lo, seed_hi, (uint32_t)bh,
+                                  (uint32_t)(qw0 + 8 * g + 4 * (lane >> 5)) >> 2,
+                                  (uint32_t)(k0 + (lane & 31)), drop_thr) << (4 * g);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       // S = Q x K^T and dP = dO x V^T in one pass.
       f32x16 s = (f32x16)(0.f);
       f32x16 dp = (f32x16)(0.f);
 #pragma unroll
       for (int ch = 0; ch < NCH; ++ch) {
         bf16x8_t kfrag = read_rm_frag<C>(ldsK, lane & 31, 16 * ch * 2 + 16 * (lane >> 5));
-        bf16x8_t qfr = (sp == SPW - 1) ? qf[ch]
+        bf16x8_t qfr = (QF_RES && sp == SPW - 1) ? qf[QF_RES ? ch : 0]
             : *(const bf16x8_t*)(qrow + 16 * ch + 8 * (lane >> 5));
         s = mfma_32x32x16_bf16(qfr, kfrag, s);
         bf16x8_t vfrag = read_rm_frag<C>(ldsV, lane & 31, 16 * ch * 2 + 16 * (lane >> 5));
@@ -993,7 +1099,9 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dq_kernel(
         const float d_r = shfl32(mydelta[sp], mfma_d_row(lane, r));
         const int kcol = k0 + (lane & 31);
         float pv = (kcol > qrow) ? 0.f : __expf(s[r] * scale - l_r);
-        ds[r] = pv * (dp[r] - d_r) * scale;
+        float dpr = dp[r];
+        if constexpr (DROP) dpr = ((keep >> r) & 1u) ? dpr * inv_keep : 0.f;
+        ds[r] = pv * (dpr - d_r) * scale;
       }
       // transpose dS through per-wave LDS -> A-frags A[q = lane&31][k]
       u16* dsl = ldsDS + w * 32 * 32;

@@ -380,6 +380,112 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dO, torch::Tensor q, torch::Te
 }
 
 // ---------------------------------------------------------------------------
+// Attention with in-kernel dropout (philox.h). Fixed dispatch: the SPW=1,
+// 2-waves/SIMD single-tile kernels with DROP=true, NW from T as above; none
+// of the experiment environment switches apply here.
+struct DropArgs {
+  uint32_t seed_lo, seed_hi, thr;
+  float inv_keep;
+};
+static DropArgs drop_args(double p, int64_t seed) {
+  TORCH_CHECK(p > 0.0 && p < 1.0, "attn dropout: 0 < p < 1 required (got ", p, ")");
+  const uint64_t s = (uint64_t)seed;
+  return {(uint32_t)s, (uint32_t)(s >> 32), attn_drop_threshold(p),
+          (float)(1.0 / (1.0 - p))};
+}
+
+std::vector<torch::Tensor> attn_fwd_dropout(torch::Tensor q, torch::Tensor k,
+                                            torch::Tensor v, double p, int64_t seed) {
+  CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v);
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn: bf16 required");
+  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
+  TORCH_CHECK(T % 128 == 0, "attn: T % 128 == 0 required (got ", T, ")");
+  TORCH_CHECK(C == 64 || C == 128, "attn: head dim 64 or 128 (got ", C, ")");
+  const DropArgs d = drop_args(p, seed);
+  auto o = torch::empty_like(q);
+  auto lse = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
+  const int NW = (T % 256 == 0) ? 8 : 4;
+  long grid = (long)B * H * (T / (NW * 32));
+  size_t smem = std::max((size_t)(4 * 32 * C * 2), (size_t)(NW * 32 * 32 * 4));
+#define LAUNCH_FWD_DROP(CC, NN)                                                 \
+  hipLaunchKernelGGL((attn_fwd_kernel<CC, NN, 1, 2, true>), dim3(grid),         \
+                     dim3(NN * 64), smem, cur_stream(),                         \
+                     (const u16*)q.data_ptr(), (const u16*)k.data_ptr(),        \
+                     (const u16*)v.data_ptr(), (u16*)o.data_ptr(),              \
+                     lse.data_ptr<float>(), B, H, T, d.seed_lo, d.seed_hi,      \
+                     d.thr, d.inv_keep)
+  if (C == 128 && NW == 8) LAUNCH_FWD_DROP(128, 8);
+  else if (C == 128) LAUNCH_FWD_DROP(128, 4);
+  else if (NW == 8) LAUNCH_FWD_DROP(64, 8);
+  else LAUNCH_FWD_DROP(64, 4);
+#undef LAUNCH_FWD_DROP
+  launch_check();
+  return {o, lse};
+}
+
+std::vector<torch::Tensor> attn_bwd_dropout(torch::Tensor dO, torch::Tensor q,
+                                            torch::Tensor k, torch::Tensor v,
+                                            torch::Tensor o, torch::Tensor lse,
+                                            double p, int64_t seed) {
+  CHECK_GPU(dO); CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v); CHECK_GPU(o); CHECK_GPU(lse);
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn: bf16 required");
+  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
+  TORCH_CHECK(T % 128 == 0, "attn: T % 128 == 0 required (got ", T, ")");
+  TORCH_CHECK(C == 64 || C == 128, "attn: head dim 64 or 128 (got ", C, ")");
+  const DropArgs d = drop_args(p, seed);
+  long N = (long)B * H * T;
+  auto delta = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
+  long dgrid = std::min((N + 3) / 4, (long)8192);
+  hipLaunchKernelGGL(attn_delta_kernel, dim3(dgrid), dim3(256), 0, cur_stream(),
+                     (const u16*)dO.data_ptr(), (const u16*)o.data_ptr(),
+                     delta.data_ptr<float>(), N, C);
+  launch_check();
+  auto dq = torch::empty_like(q);
+  auto dk = torch::empty_like(k);
+  auto dv = torch::empty_like(v);
+  const int NW = (T % 256 == 0) ? 8 : 4;
+  long grid = (long)B * H * (T / (NW * 32));
+  size_t smem_a = std::max((size_t)(2 * 4 * 32 * C) * 2 + 2 * 64 * 4,
+                           (size_t)(NW * 32 * 32 * 4));
+  size_t smem_b = std::max((size_t)(2 * 3 * 32 * C) * 2 + NW * 32 * 32 * 2,
+                           (size_t)(NW * 32 * 32 * 4));
+#define LAUNCH_BWD_DROP(CC, NN)                                                 \
+  do {                                                                          \
+    if (smem_a > 64 * 1024)                                                     \
+      hipFuncSetAttribute(reinterpret_cast<const void*>(                        \
+                              &attn_bwd_dkv_kernel<CC, NN, 0, 2, true>),        \
+                          hipFuncAttributeMaxDynamicSharedMemorySize,           \
+                          (int)smem_a);                                         \
+    if (smem_b > 64 * 1024)                                                     \
+      hipFuncSetAttribute(reinterpret_cast<const void*>(                        \
+                              &attn_bwd_dq_kernel<CC, NN, 1, 2, true>),         \
+                          hipFuncAttributeMaxDynamicSharedMemorySize,           \
+                          (int)smem_b);                                         \
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NN, 0, 2, true>), dim3(grid),   \
+                       dim3(NN * 64), smem_a, cur_stream(),                     \
+                       (const u16*)dO.data_ptr(), (const u16*)q.data_ptr(),     \
+                       (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),      \
+                       lse.data_ptr<float>(), delta.data_ptr<float>(),          \
+                       (u16*)dk.data_ptr(), (u16*)dv.data_ptr(), B, H, T,       \
+                       d.seed_lo, d.seed_hi, d.thr, d.inv_keep);                \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<CC, NN, 1, 2, true>), dim3(grid),    \
+                       dim3(NN * 64), smem_b, cur_stream(),                     \
+                       (const u16*)dO.data_ptr(), (const u16*)q.data_ptr(),     \
+                       (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),      \
+                       lse.data_ptr<float>(), delta.data_ptr<float>(),          \
+                       (u16*)dq.data_ptr(), B, H, T, d.seed_lo, d.seed_hi,      \
+                       d.thr, d.inv_keep);                                      \
+  } while (0)
+  if (C == 128 && NW == 8) LAUNCH_BWD_DROP(128, 8);
+  else if (C == 128) LAUNCH_BWD_DROP(128, 4);
+  else if (NW == 8) LAUNCH_BWD_DROP(64, 8);
+  else LAUNCH_BWD_DROP(64, 4);
+#undef LAUNCH_BWD_DROP
+  launch_check();
+  return {dq, dk, dv};
+}
+
+// ---------------------------------------------------------------------------
 torch::Tensor embedding_bwd(torch::Tensor dy, torch::Tensor idx, long V) {
   CHECK_GPU(dy); CHECK_GPU(idx);
   TORCH_CHECK(dy.scalar_type() == torch::kBFloat16, "embedding_bwd: dy bf16");
@@ -487,6 +593,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("adamw_step", &adamw_step);
   mod.def("attn_fwd", &attn_fwd);
   mod.def("attn_bwd", &attn_bwd);
+  mod.def("attn_fwd_dropout", &attn_fwd_dropout);
+  mod.def("attn_bwd_dropout", &attn_bwd_dropout);
   mod.def("embedding_bwd", &embedding_bwd);
   mod.def("gelu_fwd", &gelu_fwd);
   mod.def("gelu_bwd", &gelu_bwd);

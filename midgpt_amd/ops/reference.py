@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -69,16 +70,69 @@ def apply_rope(x: torch.Tensor, sin: torch.Tensor, cos: torch.Tensor) -> torch.T
     return out.to(x.dtype)
 
 
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0: int, k1: int):
+    """Philox4x32-10 on numpy uint64 arrays holding 32-bit values (a 32x32
+    product fits in 64 bits, so mulhi is ``>> 32``). Mirrors csrc/philox.h."""
+    lo32 = np.uint64(0xFFFFFFFF)
+    s32 = np.uint64(32)
+    m0, m1 = np.uint64(_PHILOX_M0), np.uint64(_PHILOX_M1)
+    for _ in range(10):
+        p0 = m0 * c0
+        p1 = m1 * c2
+        n0 = (p1 >> s32) ^ c1 ^ np.uint64(k0)
+        n2 = (p0 >> s32) ^ c3 ^ np.uint64(k1)
+        c1 = p1 & lo32
+        c3 = p0 & lo32
+        c0, c2 = n0, n2
+        k0 = (k0 + _PHILOX_W0) & 0xFFFFFFFF
+        k1 = (k1 + _PHILOX_W1) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def attn_dropout_threshold(p: float) -> int:
+    """(uint32)(p * 2^32): an element is kept iff its word >= this."""
+    return int(p * 4294967296.0)
+
+
+def attn_dropout_keep(seed: int, B: int, H: int, T: int, p: float) -> torch.Tensor:
+    """Bit-exact host mirror of the attention kernels' dropout keep-mask
+    (csrc/philox.h): bool (B, H, T, T), True = kept. Key = 64-bit seed,
+    counter = (k, q >> 2, b*H + h, 0), element (q, k) takes word q & 3."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    bh = np.arange(B * H, dtype=np.uint64)[:, None, None]
+    q4 = np.arange((T + 3) // 4, dtype=np.uint64)[None, :, None]
+    kk = np.arange(T, dtype=np.uint64)[None, None, :]
+    shape = (B * H, (T + 3) // 4, T)
+    c0 = np.broadcast_to(kk, shape)
+    c1 = np.broadcast_to(q4, shape)
+    c2 = np.broadcast_to(bh, shape)
+    c3 = np.zeros(shape, dtype=np.uint64)
+    words = np.stack(_philox4x32_10(c0, c1, c2, c3, k0, k1), axis=2)  # (BH,T/4,4,T)
+    keep = words.reshape(B * H, -1, T)[:, :T] >= np.uint64(attn_dropout_threshold(p))
+    return torch.from_numpy(np.ascontiguousarray(keep)).view(B, H, T, T)
+
+
 def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                     dropout_p: float = 0.0, training: bool = False) -> torch.Tensor:
+                     dropout_p: float = 0.0, training: bool = False,
+                     keep: torch.Tensor | None = None) -> torch.Tensor:
     """q,k,v: (B, H, T, C). Materialized reference (O(T^2) memory):
-    scores = QK^T masked, softmax((scores)/sqrt(C)) in fp32, then @V."""
+    scores = QK^T masked, softmax((scores)/sqrt(C)) in fp32, then @V.
+    With ``keep`` (bool, broadcastable to (B,H,T,T), e.g. from
+    ``attn_dropout_keep``) that mask replaces ``F.dropout``: kept
+    probabilities are scaled by 1/(1-dropout_p), the rest zeroed."""
     B, H, T, C = q.shape
     s = torch.matmul(q.float(), k.float().transpose(-1, -2))
     mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
     s = s.masked_fill(~mask, float("-inf"))
     a = torch.softmax(s / math.sqrt(C), dim=-1)
-    if dropout_p > 0.0 and training:
+    if keep is not None:
+        a = a * keep.to(device=a.device, dtype=a.dtype) / (1.0 - dropout_p)
+    elif dropout_p > 0.0 and training:
         a = F.dropout(a, p=dropout_p, training=True)
     return torch.matmul(a.to(v.dtype), v)
 

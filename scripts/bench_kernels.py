@@ -25,19 +25,28 @@ def timeit(fn, iters=20, warmup=5):
     return (time.perf_counter() - t0) / iters
 
 
-def bench_attn(B=32, H=16, T=1024, C=128):
+def bench_attn(B=32, H=16, T=1024, C=128, dropout_p=0.0):
     q = torch.randn(B, H, T, C, device=DEV, dtype=torch.bfloat16)
     k = torch.randn_like(q)
     v = torch.randn_like(q)
-    o, lse = ops._C.attn_fwd(q, k, v)
-    do = torch.randn_like(o)
-    t_fwd = timeit(lambda: ops._C.attn_fwd(q, k, v))
-    t_bwd = timeit(lambda: ops._C.attn_bwd(do, q, k, v, o, lse))
+    if dropout_p > 0.0:  # in-kernel Philox dropout (fixed seed)
+        fwd = lambda: ops._C.attn_fwd_dropout(q, k, v, dropout_p, 1234)
+        o, lse = fwd()
+        do = torch.randn_like(o)
+        bwd = lambda: ops._C.attn_bwd_dropout(do, q, k, v, o, lse, dropout_p, 1234)
+    else:
+        fwd = lambda: ops._C.attn_fwd(q, k, v)
+        o, lse = fwd()
+        do = torch.randn_like(o)
+        bwd = lambda: ops._C.attn_bwd(do, q, k, v, o, lse)
+    t_fwd = timeit(fwd)
+    t_bwd = timeit(bwd)
     flops_fwd = 4 * B * H * T * T * C / 2  # causal
     flops_bwd = flops_fwd * 2.5
-    print(f"attn_fwd  B{B} H{H} T{T} C{C}: {t_fwd*1e3:8.3f} ms  "
+    tag = f" p{dropout_p}" if dropout_p > 0.0 else ""
+    print(f"attn_fwd  B{B} H{H} T{T} C{C}{tag}: {t_fwd*1e3:8.3f} ms  "
           f"{flops_fwd/t_fwd/1e12:7.1f} TF/s (causal-effective)")
-    print(f"attn_bwd  B{B} H{H} T{T} C{C}: {t_bwd*1e3:8.3f} ms  "
+    print(f"attn_bwd  B{B} H{H} T{T} C{C}{tag}: {t_bwd*1e3:8.3f} ms  "
           f"{flops_bwd/t_bwd/1e12:7.1f} TF/s (causal-effective)")
 
 
@@ -127,6 +136,8 @@ if __name__ == "__main__":
         bench_attn()
         bench_attn(B=32, H=12, T=1024, C=64)
         bench_attn(B=4, H=32, T=4096, C=128)  # 7B shape
+        bench_attn(B=64, H=6, T=256, C=64)  # shakespeare_char shape
+        bench_attn(B=64, H=6, T=256, C=64, dropout_p=0.2)
     if w in ("all", "gelu"):
         bench_gelu()
     if w in ("all", "embed"):

@@ -68,13 +68,20 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
 }
 
 // ---------------------------------------------------------------------------
+// The qkv_prep kernels reduce over C/8 lanes with width-(C/8) shuffles and
+// put 64/(C/8) rows in a wave: C/8 must be a power of two that divides 64.
+static void check_qkv_head_dim(int C) {
+  TORCH_CHECK(C == 8 || C == 16 || C == 32 || C == 64 || C == 128,
+              "qkv_prep: head dim must be 8, 16, 32, 64 or 128 (got ", C, ")");
+}
+
 std::vector<torch::Tensor> qkv_prep_fwd(torch::Tensor qkv, torch::Tensor qw,
                                         torch::Tensor kw, torch::Tensor sin_t,
                                         torch::Tensor cos_t, double eps) {
   CHECK_GPU(qkv);
   TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "qkv must be bf16");
   int B = qkv.size(0), T = qkv.size(1), H = qkv.size(3), C = qkv.size(4);
-  TORCH_CHECK(C % 8 == 0 && C <= 128, "head dim must be %8==0 and <= 128");
+  check_qkv_head_dim(C);
   auto opt = qkv.options();
   auto q = torch::empty({B, H, T, C}, opt);
   auto k = torch::empty({B, H, T, C}, opt);
@@ -103,8 +110,23 @@ std::vector<torch::Tensor> qkv_prep_bwd(torch::Tensor dq, torch::Tensor dk,
                                         torch::Tensor sin_t, torch::Tensor cos_t,
                                         torch::Tensor qstats, torch::Tensor kstats,
                                         double eps) {
-  CHECK_GPU(dq); CHECK_GPU(qkv);
+  CHECK_GPU(dq); CHECK_GPU(dk); CHECK_GPU(dv); CHECK_GPU(qkv);
+  CHECK_GPU(qstats); CHECK_GPU(kstats);
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16 &&
+              dq.scalar_type() == torch::kBFloat16 &&
+              dk.scalar_type() == torch::kBFloat16 &&
+              dv.scalar_type() == torch::kBFloat16,
+              "qkv_prep_bwd: qkv, dq, dk, dv must be bf16");
+  TORCH_CHECK(qstats.scalar_type() == torch::kFloat &&
+              kstats.scalar_type() == torch::kFloat,
+              "qkv_prep_bwd: stats must be fp32");
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "qkv_prep_bwd: qkv must be (B,T,3,H,C)");
   int B = qkv.size(0), T = qkv.size(1), H = qkv.size(3), C = qkv.size(4);
+  check_qkv_head_dim(C);
+  TORCH_CHECK(dq.numel() == (long)B * H * T * C && dk.numel() == dq.numel() &&
+              dv.numel() == dq.numel() && qstats.numel() == (long)B * H * T * 2 &&
+              kstats.numel() == qstats.numel(),
+              "qkv_prep_bwd: dq/dk/dv must be (B,H,T,C) and stats (B,H,T,2)");
   auto dqkv = torch::empty_like(qkv);
   auto qwf = qw.to(torch::kFloat).contiguous();
   auto kwf = kw.to(torch::kFloat).contiguous();
@@ -114,7 +136,7 @@ std::vector<torch::Tensor> qkv_prep_bwd(torch::Tensor dq, torch::Tensor dk,
   int nblocks = (int)std::min((nrows + 3) / 4, (long)4096);
   auto dqw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
   auto dkw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
-  size_t smem = 2 * C * sizeof(float);
+  size_t smem = 4 * 2 * C * sizeof(float);  // [waves = 256/64][2][C]
   hipLaunchKernelGGL(qkv_prep_bwd_kernel, dim3(nblocks), dim3(256), smem, cur_stream(),
                      (const u16*)dq.data_ptr(), (const u16*)dk.data_ptr(),
                      (const u16*)dv.data_ptr(), (const u16*)qkv.data_ptr(),

@@ -228,11 +228,9 @@ __global__ void qkv_prep_bwd_kernel(const u16* __restrict__ dq,
   const unsigned row0 = ((unsigned)blockIdx.x * (blockDim.x / WAVE) + wave_id()) * RPW + rsub;
   const unsigned rstep = (unsigned)gridDim.x * (blockDim.x / WAVE) * RPW;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* smem = (float*)smem_raw;  // [2][C] partial dqw / dkw
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) smem[i] = 0.f;
-  __syncthreads();
+  float* smem = (float*)smem_raw;  // [waves][2][C] per-wave partial dqw / dkw
   // per-thread dw accumulators (8 q-slots + 8 k-slots at this lane's sub
-  // offset) -> ONE atomic pass at the end instead of per-row atomics
+  // offset) -> ONE reduction pass at the end instead of per-row atomics
   float dwq_acc[8] = {0}, dwk_acc[8] = {0};
   for (unsigned row = row0; row < nrows; row += rstep) {
     const unsigned h = row % (unsigned)H;
@@ -288,14 +286,36 @@ __global__ void qkv_prep_bwd_kernel(const u16* __restrict__ dq,
     }
     *(u16x8*)dst = out;
   }
+  // Block reduction in a fixed order (no atomics): the weight gradients must
+  // not depend on wave scheduling, since an activation-remat replay is
+  // compared with the plain backward bit for bit.
+  // 1) butterfly over the wave's RPW row groups (lanes with equal sub)
+  for (int o = LPR; o < WAVE; o <<= 1) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    atomicAdd(&smem[sub * 8 + j], dwq_acc[j]);
-    atomicAdd(&smem[C + sub * 8 + j], dwk_acc[j]);
+    for (int j = 0; j < 8; ++j) {
+      dwq_acc[j] += __shfl_xor(dwq_acc[j], o);
+      dwk_acc[j] += __shfl_xor(dwk_acc[j], o);
+    }
+  }
+  // 2) one row group per wave publishes the wave's totals
+  const int nw = blockDim.x / WAVE;
+  if (rsub == 0) {
+    float* mine = smem + (long)wave_id() * 2 * C;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      mine[sub * 8 + j] = dwq_acc[j];
+      mine[C + sub * 8 + j] = dwk_acc[j];
+    }
   }
   __syncthreads();
+  // 3) waves summed in index order
   for (int i = threadIdx.x; i < C; i += blockDim.x) {
-    dqw_partial[(long)blockIdx.x * C + i] = smem[i];
-    dkw_partial[(long)blockIdx.x * C + i] = smem[C + i];
+    float sq = smem[i], sk = smem[C + i];
+    for (int w2 = 1; w2 < nw; ++w2) {
+      sq += smem[w2 * 2 * C + i];
+      sk += smem[w2 * 2 * C + C + i];
+    }
+    dqw_partial[(long)blockIdx.x * C + i] = sq;
+    dkw_partial[(long)blockIdx.x * C + i] = sk;
   }
 }

@@ -85,10 +85,18 @@ class CausalSelfAttention(nn.Module):
     def _forward(self, x, sin, cos):
         B, T, D = x.shape
         qkv = self.c_attn(x).view(B, T, 3, self.n_head, self.head_dim)
+        ref_dropout = (self.dropout > 0.0 and self.training
+                       and os.environ.get("MIDGPT_ATTN_DROPOUT_REF") == "1")
+        if not ref_dropout and not ops.glue_unfused():
+            # Prep + attention without the transpose copies around it: O
+            # comes back as (B, T, D) and dV goes straight into dqkv.
+            o = ops.qkv_attention(qkv, self.q_ln_weight, self.k_ln_weight,
+                                  sin[:T], cos[:T],
+                                  self.dropout if self.training else 0.0)
+            return self.resid_dropout(self.c_proj(o))
         q, k, v = ops.qkv_prep(qkv, self.q_ln_weight, self.k_ln_weight,
                                sin[:T], cos[:T])
-        if (self.dropout > 0.0 and self.training
-                and os.environ.get("MIDGPT_ATTN_DROPOUT_REF") == "1"):
+        if ref_dropout:
             # A/B only: the materialized O(T^2) path (torch softmax +
             # F.dropout, differentiated by autograd).
             from midgpt_amd.ops import reference as refops
@@ -144,6 +152,20 @@ class Block(nn.Module):
             x = x + self.mlp(ops.rmsnorm(x, None, 1e-6))
             return x
 
+    def forward_pending(self, x, pending, sin, cos):
+        """Same block with every residual add fused into the norm that
+        follows it. The residual stream travels as (x, pending): the stream
+        before the previous branch's output has been added, and that output
+        (None ahead of the first block). Returns the pair for the next
+        block; the caller fuses the last add into the final norm."""
+        with _scope("block"):
+            if pending is None:
+                h = ops.rmsnorm(x, None, 1e-6)
+            else:
+                x, h = ops.add_rmsnorm(x, pending, 1e-6)
+            x, h = ops.add_rmsnorm(x, self.attn(h, sin, cos), 1e-6)
+            return x, self.mlp(h)
+
 
 class GPT(nn.Module):
     def __init__(self, config: GPTConfig, generator=None):
@@ -167,9 +189,25 @@ class GPT(nn.Module):
     def _block_fn(self, blk, x):
         return blk(x, self.rope_sin, self.rope_cos)
 
+    def _block_pending_fn(self, blk, x, pending):
+        return blk.forward_pending(x, pending, self.rope_sin, self.rope_cos)
+
     def forward(self, idx: torch.Tensor) -> torch.Tensor:
         """idx (B, T) int64 -> logits (B, T, V) in compute dtype."""
         x = self.drop(ops.embedding(idx, self.wte))
+        if not ops.glue_unfused():
+            pending = None
+            for blk in self.blocks:
+                if self.remat and torch.is_grad_enabled():
+                    x, pending = torch.utils.checkpoint.checkpoint(
+                        self._block_pending_fn, blk, x, pending,
+                        use_reentrant=False)
+                else:
+                    x, pending = self._block_pending_fn(blk, x, pending)
+            if pending is None:  # no blocks
+                return self.lm_head(ops.rmsnorm(x, None, 1e-5))
+            _, h = ops.add_rmsnorm(x, pending, 1e-5)
+            return self.lm_head(h)
         for blk in self.blocks:
             if self.remat and torch.is_grad_enabled():
                 x = torch.utils.checkpoint.checkpoint(

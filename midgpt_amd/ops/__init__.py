@@ -105,6 +105,56 @@ def rmsnorm(x, weight=None, eps: float = 1e-6):
     return _RMSNorm.apply(x, weight, eps)
 
 
+def glue_unfused() -> bool:
+    """MIDGPT_GLUE_UNFUSED=1 (read at call time) restores the composition of
+    separate add, rmsnorm, qkv_prep, flash_attention and transpose kernels:
+    the A/B handle for ``add_rmsnorm`` / ``qkv_attention`` and the path the
+    tests compare them against, bit for bit."""
+    return os.environ.get("MIDGPT_GLUE_UNFUSED") == "1"
+
+
+# ----------------------------------------------------------------------------
+# Fused residual add + weightless RMSNorm: s = x + r, y = rmsnorm(s).
+# One kernel each way instead of add + norm (forward) and norm-backward +
+# gradient-accumulation add (backward); results are bit-identical to those.
+# ----------------------------------------------------------------------------
+class _AddRMSNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, r, eps):
+        shp = x.shape
+        D = shp[-1]
+        s, y, invrms = _C.add_rmsnorm_fwd(x.reshape(-1, D).contiguous(),
+                                          r.reshape(-1, D).contiguous(), eps)
+        ctx.save_for_backward(s, invrms)
+        ctx.set_materialize_grads(False)
+        return s.view(shp), y.view(shp)
+
+    @staticmethod
+    def backward(ctx, ds, dy):
+        s, invrms = ctx.saved_tensors
+        if dy is None:  # only the sum was used
+            return ds, ds, None
+        shp = dy.shape
+        if ds is not None:
+            ds = ds.reshape(s.shape).contiguous()
+        dx = _C.add_rmsnorm_bwd(ds, dy.reshape(s.shape).contiguous(), s,
+                                invrms).view(shp)
+        # d(x + r) flows to both addends unchanged: one tensor serves both
+        return dx, dx, None
+
+
+def add_rmsnorm(x, r, eps: float = 1e-6):
+    """(s, y) with s = x + r and y = rmsnorm(s) (weightless). On GPU in bf16
+    with D % 8 == 0 this is one fused kernel per direction; otherwise (CPU,
+    other dtypes or widths) the composition of the existing ops."""
+    if (_use_hip(x, r) and x.dtype == torch.bfloat16 and r.dtype == torch.bfloat16
+            and x.shape == r.shape and x.shape[-1] % 8 == 0
+            and not glue_unfused()):
+        return _AddRMSNorm.apply(x, r, eps)
+    s = x + r
+    return s, rmsnorm(s, None, eps)
+
+
 # ----------------------------------------------------------------------------
 # Fused QK-LayerNorm + RoPE over the packed QKV projection
 # (reference src/model.py:59-69; plan K3+K4). Input qkv: (B, T, 3, H, C)
@@ -289,17 +339,85 @@ def flash_attention(q, k, v, dropout_p: float = 0.0, seed: int | None = None):
     (fwd + bwd) with a counter-based mask keyed by ``seed``; with
     ``seed=None`` the seed is drawn by ``draw_dropout_seed``.
     ``dropout_p == 0`` is exactly the undropped path."""
-    dropout_p = float(dropout_p)
+    dropout_p, seed = _resolve_dropout(dropout_p, seed, "flash_attention")
     if dropout_p == 0.0:
         return _Attention.apply(q, k, v)
+    return _Attention.apply(q, k, v, dropout_p, seed)
+
+
+def _resolve_dropout(dropout_p, seed, who):
+    """(p, seed as the int64 the bindings take); seed drawn if p > 0 and
+    none was given."""
+    dropout_p = float(dropout_p)
+    if dropout_p == 0.0:
+        return 0.0, 0
     if not 0.0 < dropout_p < 1.0:
-        raise ValueError(f"flash_attention: dropout_p must be in [0, 1), got {dropout_p}")
+        raise ValueError(f"{who}: dropout_p must be in [0, 1), got {dropout_p}")
     if seed is None:
         seed = draw_dropout_seed()
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     if seed >= 1 << 63:  # the binding takes the same 64 bits as an int64
         seed -= 1 << 64
-    return _Attention.apply(q, k, v, dropout_p, seed)
+    return dropout_p, seed
+
+
+# ----------------------------------------------------------------------------
+# QK-LayerNorm + RoPE + causal attention over the packed projection with the
+# layout copies around attention removed: qkv (B,T,3,H,C) -> o (B,T,H*C).
+# The forward kernels write O as (B,T,H,C), what the output projection reads;
+# the backward's delta kernel reads dO in that layout and re-lays it out for
+# the dkv/dq kernels on the way; dkv writes dV into slot 2 of dqkv and the Q/K
+# prep backward fills slots 0 and 1. Same arithmetic, bit for bit, as
+# qkv_prep + flash_attention + transpose.
+# MIDGPT_ATTN_PACKED_V=1 (read at call time) trades time for memory: no V copy
+# at all, the kernels read V in place from slot 2 of qkv (one (B,T,H,C)
+# activation less per layer, slower attention kernels).
+# ----------------------------------------------------------------------------
+class _QKVAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, qw, kw, sin, cos, dropout_p, seed, eps):
+        B, T, three, H, C = qkv.shape
+        assert three == 3
+        qkv = qkv.contiguous()
+        if os.environ.get("MIDGPT_ATTN_PACKED_V") == "1":
+            q, k, qstats, kstats = _C.qk_prep_fwd(qkv, qw, kw, sin, cos, eps)
+            v = qkv
+        else:
+            q, k, v, qstats, kstats = _C.qkv_prep_fwd(qkv, qw, kw, sin, cos, eps)
+        o, lse = _C.attn_fwd_packed(q, k, v, dropout_p, seed)
+        ctx.save_for_backward(qkv, qw, kw, sin, cos, q, k, v, o, lse, qstats, kstats)
+        ctx.dropout_p, ctx.seed = dropout_p, seed
+        return o.view(B, T, H * C)
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, qw, kw, sin, cos, q, k, v, o, lse, qstats, kstats = ctx.saved_tensors
+        B, T, _, H, C = qkv.shape
+        dqkv = torch.empty_like(qkv)
+        dq, dk = _C.attn_bwd_packed(do.reshape(B, T, H, C).contiguous(), q, k,
+                                    v, o, lse, dqkv, ctx.dropout_p, ctx.seed)
+        dqw, dkw = _C.qk_prep_bwd(dq, dk, qkv, qw, kw, sin, cos, qstats,
+                                  kstats, dqkv)
+        return dqkv, dqw, dkw, None, None, None, None, None
+
+
+def qkv_attention(qkv, q_ln_weight, k_ln_weight, sin, cos,
+                  dropout_p: float = 0.0, seed: int | None = None,
+                  eps: float = 1e-6):
+    """qkv (B,T,3,H,C) -> causal attention output (B,T,H*C).
+
+    Dropout and seed as in ``flash_attention``: the seed is drawn on the
+    host, so a ``torch.utils.checkpoint`` replay regenerates the same mask.
+    Off the GPU (and under MIDGPT_GLUE_UNFUSED=1) this is the composition
+    qkv_prep -> flash_attention -> transpose."""
+    B, T, _, H, C = qkv.shape
+    if _use_hip(qkv) and not glue_unfused():
+        dropout_p, seed = _resolve_dropout(dropout_p, seed, "qkv_attention")
+        return _QKVAttention.apply(qkv, q_ln_weight, k_ln_weight, sin, cos,
+                                   dropout_p, seed, eps)
+    q, k, v = qkv_prep(qkv, q_ln_weight, k_ln_weight, sin, cos, eps)
+    o = flash_attention(q, k, v, dropout_p, seed)
+    return o.transpose(1, 2).reshape(B, T, H * C)
 
 
 # ----------------------------------------------------------------------------

@@ -22,6 +22,21 @@
 #include "philox.h"
 
 // ---------------------------------------------------------------------------
+// Operand addressing. Q, K, dQ, dK, LSE and delta are always (B,H,T,*)
+// packed. O, dO, V and dV carry explicit strides in elements (the head dim
+// is contiguous), so the same kernels serve the (B,H,T,C) layout, O/dO kept
+// as (B,T,H,C) — what the output projection consumes, no transpose copy —
+// and V/dV living in slot 2 of the packed (B,T,3,H,C) projection.
+// ---------------------------------------------------------------------------
+struct AttnStrides {
+  long b, h;  // batch and head stride
+  int r;      // row (t) stride
+};
+DEVINL long bh_base(const AttnStrides& s, long bh, int H) {
+  return (bh / H) * s.b + (bh % H) * s.h;
+}
+
+// ---------------------------------------------------------------------------
 // LDS swizzles
 // ---------------------------------------------------------------------------
 // Row-major [R][C] bf16 tile, rows of C*2 bytes, read by ds_read_b128 at
@@ -43,17 +58,22 @@ DEVINL int swz_tr(int row, int byte_in_row) {
 // latency hides under the MFMA phase instead of stalling the wave at a
 // vmcnt before its LDS writes).
 // ---------------------------------------------------------------------------
+// ld = row stride of the global tile, in elements. The per-thread offset
+// row*ld + col is 32-bit and loop-invariant; only the wave-uniform tile base g
+// advances from tile to tile.
 // Single-row loader -> row-major swizzled image only.
 template <int C, int NT>
 struct RmStage {
   static constexpr int NV = (32 * C + NT * 8 - 1) / (NT * 8);
   u16x8 v[NV];
-  DEVINL void load(const u16* __restrict__ g) {
+  DEVINL void load(const u16* __restrict__ g, int ld = C) {
+    static_assert((NT * 8) % C == 0, "a thread keeps its column across loads");
+    const int idx0 = threadIdx.x * 8;
+    const unsigned boff = 2u * (unsigned)((idx0 / C) * ld + idx0 % C);  // bytes
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int idx = threadIdx.x * 8 + i * NT * 8;
-      if (idx < 32 * C)
-        v[i] = *(const u16x8*)(g + (long)(idx / C) * C + idx % C);
+      if (idx0 + i * NT * 8 < 32 * C)
+        v[i] = *(const u16x8*)((const char*)(g + (long)(i * (NT * 8 / C)) * ld) + boff);
     }
   }
   DEVINL void write(u16* lds) const {
@@ -73,15 +93,24 @@ template <int C, int NT>
 struct TrStage {
   static constexpr int NP = (32 * C + NT * 16 - 1) / (NT * 16);
   u16x8 a[NP], b[NP];  // rows 2p and 2p+1 at an 8-col span
-  DEVINL void load(const u16* __restrict__ g) {
+  DEVINL void load(const u16* __restrict__ g, int ld = C) {
+    static_assert((NT * 8) % C == 0, "a thread keeps its column across loads");
+    const int idx0 = threadIdx.x * 16;
+    const unsigned boff =  // bytes
+        2u * (unsigned)(2 * (idx0 / (2 * C)) * ld + (idx0 / 2) % C);
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      const int idx = threadIdx.x * 16 + i * NT * 16;
-      if (idx >= 32 * C) continue;
-      const int row = 2 * (idx / (2 * C));
-      const int col = (idx / 2) % C;
-      a[i] = *(const u16x8*)(g + (long)row * C + col);
-      b[i] = *(const u16x8*)(g + (long)(row + 1) * C + col);
+      if (idx0 + i * NT * 16 >= 32 * C) continue;
+      // row pair i of this thread: 2 * (NT * 8 / C) rows further down
+      const u16* gi = g + (long)(i * 2 * (NT * 8 / C)) * ld;
+      const char* pa = (const char*)gi + boff;
+      // Row 2p+1 sits one (wave-uniform, runtime) row stride after row 2p.
+      // Kept opaque so that the second address is formed from the first at
+      // issue time, not carried through the tile loop as a pointer of its own.
+      int ldb = 2 * ld;
+      asm volatile("" : "+s"(ldb));
+      a[i] = *(const u16x8*)pa;
+      b[i] = *(const u16x8*)(pa + ldb);
     }
   }
   DEVINL void write_tr(u16* lds) const {
@@ -113,12 +142,12 @@ struct TrStage {
 };
 // Synchronous convenience wrappers (prologue use).
 template <int C, int NT>
-DEVINL void stage_rm(const u16* __restrict__ g, u16* lds) {
-  RmStage<C, NT> st; st.load(g); st.write(lds);
+DEVINL void stage_rm(const u16* __restrict__ g, u16* lds, int ld = C) {
+  RmStage<C, NT> st; st.load(g, ld); st.write(lds);
 }
 template <int C, int NT>
-DEVINL void stage_tr(const u16* __restrict__ g, u16* lds) {
-  TrStage<C, NT> st; st.load(g); st.write_tr(lds);
+DEVINL void stage_tr(const u16* __restrict__ g, u16* lds, int ld = C) {
+  TrStage<C, NT> st; st.load(g, ld); st.write_tr(lds);
 }
 
 // Read one A/B fragment (bf16x8) from a swizzled row-major [R][C] tile:
@@ -173,6 +202,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_fwd_kernel(const u16* __re
                                 const u16* __restrict__ v,
                                 u16* __restrict__ o, float* __restrict__ lse,
                                 int B, int H, int T,
+                                AttnStrides sv, AttnStrides so,
                                 uint32_t seed_lo = 0, uint32_t seed_hi = 0,
                                 uint32_t drop_thr = 0, float inv_keep = 1.f) {
   constexpr int NCB = C / 32;   // 32-col c-blocks
@@ -197,7 +227,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_fwd_kernel(const u16* __re
 
   const u16* qg = q + (bh * T) * C;
   const u16* kg = k + (bh * T) * C;
-  const u16* vg = v + (bh * T) * C;
+  const u16* vg = v + bh_base(sv, bh, H);
 
   // Q B-fragments in registers for the LAST (busiest) strip only; earlier
   // strips re-read their Q rows from global per tile (L2-resident, few
@@ -221,7 +251,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_fwd_kernel(const u16* __re
 
   const int nkt = (q0 + NSTRIP * 32) / 32;
   stage_rm<C, NW * 64>(kg, ldsK);
-  stage_tr<C, NW * 64>(vg, ldsVt);
+  stage_tr<C, NW * 64>(vg, ldsVt, sv.r);
   __syncthreads();
 
   RmStage<C, NW * 64> kst;
@@ -231,7 +261,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_fwd_kernel(const u16* __re
     const bool pre = kt + 1 < nkt;
     if (pre) {  // T14: issue next tile's loads before this tile's compute
       kst.load(kg + (long)(kt + 1) * 32 * C);
-      vst.load(vg + (long)(kt + 1) * 32 * C);
+      vst.load(vg + (long)(kt + 1) * 32 * sv.r, sv.r);
     }
     const int k0 = kt * 32;
 #pragma unroll
@@ -336,7 +366,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_fwd_kernel(const u16* __re
     for (int r = 0; r < 16; ++r) rrow[r] = shfl32(rec, mfma_d_row(lane, r));
     if (lane < 32) lse[bh * T + myq] = m[sp] * scale + __logf(lsum[sp]);
     float* ob = obuf + w * 32 * 32;
-    u16* og = o + (bh * T + qw0) * C;
+    u16* og = o + bh_base(so, bh, H) + (long)qw0 * so.r;
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
 #pragma unroll
@@ -357,8 +387,8 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_fwd_kernel(const u16* __re
       u16x8 out0, out1;
 #pragma unroll
       for (int j = 0; j < 8; ++j) { out0[j] = f2b(tmp[j]); out1[j] = f2b(tmp[8 + j]); }
-      *(u16x8*)(og + (long)row * C + 32 * cb + c16) = out0;
-      *(u16x8*)(og + (long)row * C + 32 * cb + c16 + 8) = out1;
+      *(u16x8*)(og + (long)row * so.r + 32 * cb + c16) = out0;
+      *(u16x8*)(og + (long)row * so.r + 32 * cb + c16 + 8) = out1;
       __builtin_amdgcn_s_waitcnt(0);
     }
   }
@@ -376,7 +406,7 @@ template <int C, int NW>
 __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d2_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, u16* __restrict__ o, float* __restrict__ lse,
-    int B, int H, int T) {
+    int B, int H, int T, AttnStrides sv, AttnStrides so) {
   constexpr int NCB = C / 32;
   constexpr int NCH = C / 16;
   const float scale = rsqrtf((float)C);
@@ -395,7 +425,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d2_kernel(
 
   const u16* qg = q + (bh * T) * C;
   const u16* kg = k + (bh * T) * C;
-  const u16* vg = v + (bh * T) * C;
+  const u16* vg = v + bh_base(sv, bh, H);
 
   bf16x8_t qf[NCH];
   {
@@ -462,17 +492,17 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d2_kernel(
 
   // prologue: tile 0 staged synchronously; tile 1's loads issued (stO)
   stage_rm<C, NW * 64>(kg, ldsK);
-  stage_tr<C, NW * 64>(vg, ldsVt);
+  stage_tr<C, NW * 64>(vg, ldsVt, sv.r);
   RmStage<C, NW * 64> kE, kO;
   TrStage<C, NW * 64> vE, vO;
-  if (1 < nkt) { kO.load(kg + (long)32 * C); vO.load(vg + (long)32 * C); }
+  if (1 < nkt) { kO.load(kg + (long)32 * C); vO.load(vg + (long)32 * sv.r, sv.r); }
   __syncthreads();
 
 #define FWD_D2_STEP(J, ST_LD, ST_WR, LBUF, WBUF)                              \
   do {                                                                        \
     if (kt + (J) + 2 < nkt) {                                                 \
       k##ST_LD.load(kg + (long)(kt + (J) + 2) * 32 * C);                      \
-      v##ST_LD.load(vg + (long)(kt + (J) + 2) * 32 * C);                      \
+      v##ST_LD.load(vg + (long)(kt + (J) + 2) * 32 * sv.r, sv.r);             \
     }                                                                         \
     tile_compute(kt + (J), ldsK + (LBUF) * 32 * C, ldsVt + (LBUF) * C * 32);  \
     if (kt + (J) + 1 < nkt) {                                                 \
@@ -498,7 +528,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d2_kernel(
   for (int r = 0; r < 16; ++r) rrow[r] = shfl32(rec, mfma_d_row(lane, r));
   if (lane < 32) lse[bh * T + myq] = m * scale + __logf(lsum);
   float* ob = obuf + w * 32 * 32;
-  u16* og = o + (bh * T + qw0) * C;
+  u16* og = o + bh_base(so, bh, H) + (long)qw0 * so.r;
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) {
 #pragma unroll
@@ -519,8 +549,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d2_kernel(
     u16x8 out0, out1;
 #pragma unroll
     for (int j = 0; j < 8; ++j) { out0[j] = f2b(tmp[j]); out1[j] = f2b(tmp[8 + j]); }
-    *(u16x8*)(og + (long)row * C + 32 * cb + c16) = out0;
-    *(u16x8*)(og + (long)row * C + 32 * cb + c16 + 8) = out1;
+    *(u16x8*)(og + (long)row * so.r + 32 * cb + c16) = out0;
+    *(u16x8*)(og + (long)row * so.r + 32 * cb + c16 + 8) = out1;
     __builtin_amdgcn_s_waitcnt(0);
   }
 }
@@ -530,11 +560,13 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d2_kernel(
 // merged online-softmax rescale — halves barrier rounds and O-rescale
 // passes vs the single-tile loop. nkt is always even (multiple of NW).
 // ===========================================================================
+// C=64 fits 3 waves/SIMD (168 VGPRs): ask for it rather than leave it to
+// the allocator's choice under a 2-wave bound.
 template <int C, int NW>
-__global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
+__global__ __launch_bounds__(NW * 64, C == 64 ? 3 : 2) void attn_fwd2_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, u16* __restrict__ o, float* __restrict__ lse,
-    int B, int H, int T) {
+    int B, int H, int T, AttnStrides sv, AttnStrides so) {
   constexpr int NCB = C / 32;
   constexpr int NCH = C / 16;
   const float scale = rsqrtf((float)C);
@@ -553,7 +585,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
 
   const u16* qg = q + (bh * T) * C;
   const u16* kg = k + (bh * T) * C;
-  const u16* vg = v + (bh * T) * C;
+  const u16* vg = v + bh_base(sv, bh, H);
 
   bf16x8_t qf[NCH];
   {
@@ -571,8 +603,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
   // prologue: stage round 0 (two tiles) synchronously
   stage_rm<C, NW * 64>(kg, ldsK);
   stage_rm<C, NW * 64>(kg + 32 * C, ldsK + 32 * C);
-  stage_tr<C, NW * 64>(vg, ldsVt);
-  stage_tr<C, NW * 64>(vg + 32 * C, ldsVt + C * 32);
+  stage_tr<C, NW * 64>(vg, ldsVt, sv.r);
+  stage_tr<C, NW * 64>(vg + (long)32 * sv.r, ldsVt + C * 32, sv.r);
   __syncthreads();
 
   RmStage<C, NW * 64> kstA, kstB;
@@ -584,8 +616,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
       const long nb = (long)(rd + 1) * 64;
       kstA.load(kg + nb * C);
       kstB.load(kg + (nb + 32) * C);
-      vstA.load(vg + nb * C);
-      vstB.load(vg + (nb + 32) * C);
+      vstA.load(vg + nb * sv.r, sv.r);
+      vstB.load(vg + (nb + 32) * sv.r, sv.r);
     }
     const int k0 = rd * 64;
     if (k0 <= qw0 + 31) {  // at least sub-tile A needed by this wave
@@ -681,7 +713,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
   for (int r = 0; r < 16; ++r) rrow[r] = shfl32(rec, mfma_d_row(lane, r));
   if (lane < 32) lse[bh * T + myq] = m * scale + __logf(lsum);
   float* ob = obuf + w * 32 * 32;
-  u16* og = o + (bh * T + qw0) * C;
+  u16* og = o + bh_base(so, bh, H) + (long)qw0 * so.r;
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) {
 #pragma unroll
@@ -702,8 +734,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
     u16x8 out0, out1;
 #pragma unroll
     for (int j = 0; j < 8; ++j) { out0[j] = f2b(tmp[j]); out1[j] = f2b(tmp[8 + j]); }
-    *(u16x8*)(og + (long)row * C + 32 * cb + c16) = out0;
-    *(u16x8*)(og + (long)row * C + 32 * cb + c16 + 8) = out1;
+    *(u16x8*)(og + (long)row * so.r + 32 * cb + c16) = out0;
+    *(u16x8*)(og + (long)row * so.r + 32 * cb + c16 + 8) = out1;
     __builtin_amdgcn_s_waitcnt(0);
   }
 }
@@ -713,22 +745,44 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
 // Unchanged under dropout: with O_i = sum_j P_ij Z_ij V_j (Z = keep/(1-p)),
 // dO_i.O_i = sum_j P_ij Z_ij (dO_i.V_j) = sum_j P_ij dP_ij, dP = (dO V^T)oZ.
 // ===========================================================================
+// delta is (B,H,T) packed; dO and O are strided. bth_order: the rows are
+// visited in (b,t,h) order, the memory order of (B,T,H,C) operands, instead
+// of (b,h,t). do_copy != nullptr: dO is also written out as packed (B,H,T,C)
+// on the way, for the dkv and dq kernels to stage from (their per-head tiles
+// are then contiguous; read in place from (B,T,H,C), whose rows of one head
+// lie H*C elements apart, both kernels measured 8-12% slower).
 __global__ void attn_delta_kernel(const u16* __restrict__ dO,
                                   const u16* __restrict__ O,
-                                  float* __restrict__ delta, long N, int C) {
+                                  float* __restrict__ delta, long N, int C,
+                                  int H, int T, AttnStrides sdo, AttnStrides so,
+                                  u16* __restrict__ do_copy, int bth_order) {
   const int lane = lane_id();
   const long row0 = (long)blockIdx.x * (blockDim.x / WAVE) + wave_id();
   const long rstep = (long)gridDim.x * (blockDim.x / WAVE);
   for (long row = row0; row < N; row += rstep) {
+    // N < 2^31 (checked by the launcher): 32-bit divisions
+    const unsigned urow = (unsigned)row;
+    long bh, t;
+    if (bth_order) {
+      const unsigned bt = urow / (unsigned)H;
+      t = bt % (unsigned)T;
+      bh = (long)(bt / (unsigned)T) * H + urow % (unsigned)H;
+    } else {
+      bh = urow / (unsigned)T;
+      t = urow % (unsigned)T;
+    }
+    const u16* dor = dO + bh_base(sdo, bh, H) + t * sdo.r;
+    const u16* orow = O + bh_base(so, bh, H) + t * so.r;
     float acc = 0.f;
     for (int i = lane * 8; i < C; i += WAVE * 8) {
-      u16x8 a = *(const u16x8*)(dO + row * C + i);
-      u16x8 b = *(const u16x8*)(O + row * C + i);
+      u16x8 a = *(const u16x8*)(dor + i);
+      u16x8 b = *(const u16x8*)(orow + i);
+      if (do_copy) *(u16x8*)(do_copy + (bh * T + t) * C + i) = a;
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc += b2f(a[j]) * b2f(b[j]);
     }
     acc = group_sum<WAVE>(acc);
-    if (lane == 0) delta[row] = acc;
+    if (lane == 0) delta[bh * T + t] = acc;
   }
 }
 
@@ -750,6 +804,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
     const u16* __restrict__ k, const u16* __restrict__ v,
     const float* __restrict__ lse, const float* __restrict__ delta,
     u16* __restrict__ dk, u16* __restrict__ dv, int B, int H, int T,
+    AttnStrides sdo, AttnStrides sv, AttnStrides sdv,
     uint32_t seed_lo = 0, uint32_t seed_hi = 0, uint32_t drop_thr = 0,
     float inv_keep = 1.f) {
   constexpr int NCB = C / 32;
@@ -770,10 +825,10 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
 
   const u16* qg = q + (bh * T) * C;
   const u16* kg = k + (bh * T) * C;
-  const u16* vg = v + (bh * T) * C;
-  const u16* dog = dO + (bh * T) * C;
+  const u16* vg = v + bh_base(sv, bh, H);
+  const u16* dog = dO + bh_base(sdo, bh, H);
   const u16* krow = kg + (long)myk * C;
-  const u16* vrow = vg + (long)myk * C;
+  const u16* vrow = vg + (long)myk * sv.r;
 
   // K row fragments resident in registers (the L2 re-read variant was
   // measured -20% on dkv C=128 in a full-step profile despite removing
@@ -802,8 +857,8 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
     u16* bq = base + buf * TILE;
     stage_rm<C, NW * 64>(qg + qbase * C, bq);
     stage_tr<C, NW * 64>(qg + qbase * C, bq + 32 * C);
-    stage_rm<C, NW * 64>(dog + qbase * C, bq + 2 * 32 * C);
-    stage_tr<C, NW * 64>(dog + qbase * C, bq + 3 * 32 * C);
+    stage_rm<C, NW * 64>(dog + qbase * sdo.r, bq + 2 * 32 * C, sdo.r);
+    stage_tr<C, NW * 64>(dog + qbase * sdo.r, bq + 3 * 32 * C, sdo.r);
     if (threadIdx.x < 32) {
       ldsLse[buf * 32 + threadIdx.x] = lse[bh * T + qbase + threadIdx.x];
       ldsDelta[buf * 32 + threadIdx.x] = delta[bh * T + qbase + threadIdx.x];
@@ -820,7 +875,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
     if (ABLATE != 2 && pre) {  // T14 split: loads early
       const long nb = (long)(qt + 1) * 32;
       qst.load(qg + nb * C);
-      dost.load(dog + nb * C);
+      dost.load(dog + nb * sdo.r, sdo.r);
       if (threadIdx.x < 32) {
         lse_r = lse[bh * T + nb + threadIdx.x];
         del_r = delta[bh * T + nb + threadIdx.x];
@@ -941,11 +996,12 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
   // epilogue: LDS bounce -> wide bf16 stores (reuses the staging region)
   float* ob = (float*)smem + w * 32 * 32;
   u16* dkg = dk + (bh * T + kw0) * C;
-  u16* dvg = dv + (bh * T + kw0) * C;
+  u16* dvg = dv + bh_base(sdv, bh, H) + (long)kw0 * sdv.r;
 #pragma unroll
   for (int which = 0; which < 2; ++which) {
     f32x16* acc = which == 0 ? dkacc : dvacc;
     u16* out = which == 0 ? dkg : dvg;
+    const int old = which == 0 ? C : sdv.r;
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
 #pragma unroll
@@ -969,8 +1025,8 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
       u16x8 o0, o1;
 #pragma unroll
       for (int j = 0; j < 8; ++j) { o0[j] = f2b(tmp[j]); o1[j] = f2b(tmp[8 + j]); }
-      *(u16x8*)(out + (long)row * C + 32 * cb + c16) = o0;
-      *(u16x8*)(out + (long)row * C + 32 * cb + c16 + 8) = o1;
+      *(u16x8*)(out + (long)row * old + 32 * cb + c16) = o0;
+      *(u16x8*)(out + (long)row * old + 32 * cb + c16 + 8) = o1;
       __builtin_amdgcn_s_waitcnt(0);
     }
   }
@@ -989,6 +1045,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dq_kernel(
     const u16* __restrict__ k, const u16* __restrict__ v,
     const float* __restrict__ lse, const float* __restrict__ delta,
     u16* __restrict__ dq, int B, int H, int T,
+    AttnStrides sdo, AttnStrides sv,
     uint32_t seed_lo = 0, uint32_t seed_hi = 0, uint32_t drop_thr = 0,
     float inv_keep = 1.f) {
   constexpr int NCB = C / 32;
@@ -1011,8 +1068,8 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dq_kernel(
 
   const u16* qg = q + (bh * T) * C;
   const u16* kg = k + (bh * T) * C;
-  const u16* vg = v + (bh * T) * C;
-  const u16* dog = dO + (bh * T) * C;
+  const u16* vg = v + bh_base(sv, bh, H);
+  const u16* dog = dO + bh_base(sdo, bh, H);
 
   // Under DROP at C=128 the keep mask does not fit beside 32 VGPRs of
   // resident Q (the DROP=false kernel uses 255 of 256), so that variant
@@ -1041,7 +1098,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dq_kernel(
     const long k0 = (long)kt * 32;
     u16* bk = base + buf * TILE;
     stage_rm<C, NW * 64>(kg + k0 * C, bk);
-    stage_rm<C, NW * 64>(vg + k0 * C, bk + 32 * C);
+    stage_rm<C, NW * 64>(vg + k0 * sv.r, bk + 32 * C, sv.r);
     stage_tr<C, NW * 64>(kg + k0 * C, bk + 2 * 32 * C);
   };
   stage_set(0, 0);
@@ -1053,7 +1110,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dq_kernel(
     const bool pre = kt + 1 < nkt;
     if (pre) {
       kst.load(kg + (long)(kt + 1) * 32 * C);
-      vst.load(vg + (long)(kt + 1) * 32 * C);
+      vst.load(vg + (long)(kt + 1) * 32 * sv.r, sv.r);
     }
     const int k0 = kt * 32;
     const u16* ldsK = base + buf * TILE;
@@ -1064,7 +1121,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dq_kernel(
       const int qw0 = q0 + 32 * strip[sp];
       if (k0 > qw0 + 31) continue;
       const u16* qrow = qg + (long)(qw0 + (lane & 31)) * C;
-      const u16* dorow = dog + (long)(qw0 + (lane & 31)) * C;
+      const u16* dorow = dog + (long)(qw0 + (lane & 31)) * sdo.r;
       // DROP: bit r = keep(q of reg r, kcol). Evaluated before the MFMA
       // phase, while s/dp/ds are dead, and fenced so the Philox
       // temporaries never overlap them (the kernel sits at the VGPR cap).

@@ -67,6 +67,70 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
   return {dx, torch::Tensor()};
 }
 
+// Fused residual add + RMSNorm (weightless, bf16, D % 8 == 0). Launch
+// geometry of rmsnorm_fwd / rmsnorm_bwd: one wave per row, 4 per block.
+#define LAUNCH_BY_ROW_WIDTH(KERNEL, ...)                                        \
+  do {                                                                          \
+    if (D <= 2048)                                                              \
+      hipLaunchKernelGGL((KERNEL<4>), dim3(grid), dim3(256), 0, cur_stream(),   \
+                         __VA_ARGS__);                                          \
+    else if (D <= 4096)                                                         \
+      hipLaunchKernelGGL((KERNEL<8>), dim3(grid), dim3(256), 0, cur_stream(),   \
+                         __VA_ARGS__);                                          \
+    else                                                                        \
+      hipLaunchKernelGGL((KERNEL<0>), dim3(grid), dim3(256), 0, cur_stream(),   \
+                         __VA_ARGS__);                                          \
+  } while (0)
+
+std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x, torch::Tensor r, double eps) {
+  CHECK_GPU(x); CHECK_GPU(r);
+  TORCH_CHECK(x.dim() == 2 && r.sizes() == x.sizes(), "add_rmsnorm: x, r must be (N, D)");
+  long N = x.size(0);
+  int D = x.size(1);
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
+              r.scalar_type() == torch::kBFloat16 && D % 8 == 0,
+              "add_rmsnorm: bf16 with D%8==0 required");
+  auto s = torch::empty_like(x);
+  auto y = torch::empty_like(x);
+  auto invrms = torch::empty({N}, x.options().dtype(torch::kFloat));
+  long grid = std::min((N + 3) / 4, (long)8192);
+  if (N > 0)
+    LAUNCH_BY_ROW_WIDTH(add_rmsnorm_fwd_bf16, (const u16*)x.data_ptr(),
+                        (const u16*)r.data_ptr(), (u16*)s.data_ptr(),
+                        (u16*)y.data_ptr(), invrms.data_ptr<float>(), N, D, (float)eps);
+  launch_check();
+  return {s, y, invrms};
+}
+
+torch::Tensor add_rmsnorm_bwd(c10::optional<torch::Tensor> ds, torch::Tensor dy,
+                              torch::Tensor s, torch::Tensor invrms) {
+  CHECK_GPU(dy); CHECK_GPU(s); CHECK_GPU(invrms);
+  TORCH_CHECK(s.dim() == 2 && dy.sizes() == s.sizes(), "add_rmsnorm_bwd: dy, s must be (N, D)");
+  long N = s.size(0);
+  int D = s.size(1);
+  TORCH_CHECK(s.scalar_type() == torch::kBFloat16 &&
+              dy.scalar_type() == torch::kBFloat16 && D % 8 == 0,
+              "add_rmsnorm_bwd: bf16 with D%8==0 required");
+  TORCH_CHECK(invrms.scalar_type() == torch::kFloat && invrms.numel() == N,
+              "add_rmsnorm_bwd: invrms must be fp32 (N,)");
+  const u16* dsp = nullptr;
+  if (ds.has_value()) {
+    CHECK_GPU((*ds));
+    TORCH_CHECK(ds->scalar_type() == torch::kBFloat16 && ds->sizes() == s.sizes(),
+                "add_rmsnorm_bwd: ds must be bf16 (N, D)");
+    dsp = (const u16*)ds->data_ptr();
+  }
+  auto dx = torch::empty_like(s);
+  long grid = std::min((N + 3) / 4, (long)8192);
+  if (N > 0)
+    LAUNCH_BY_ROW_WIDTH(add_rmsnorm_bwd_bf16, dsp, (const u16*)dy.data_ptr(),
+                        (const u16*)s.data_ptr(), invrms.data_ptr<float>(),
+                        (u16*)dx.data_ptr(), N, D);
+  launch_check();
+  return dx;
+}
+#undef LAUNCH_BY_ROW_WIDTH
+
 // ---------------------------------------------------------------------------
 // The qkv_prep kernels reduce over C/8 lanes with width-(C/8) shuffles and
 // put 64/(C/8) rows in a wave: C/8 must be a power of two that divides 64.
@@ -94,7 +158,7 @@ std::vector<torch::Tensor> qkv_prep_fwd(torch::Tensor qkv, torch::Tensor qw,
   auto cf = cos_t.to(torch::kFloat).contiguous();
   long nrows = (long)B * T * H * 3;
   long grid = std::min((nrows + 3) / 4, (long)16384);
-  hipLaunchKernelGGL(qkv_prep_fwd_kernel, dim3(grid), dim3(256), 0, cur_stream(),
+  hipLaunchKernelGGL(qkv_prep_fwd_kernel<3>, dim3(grid), dim3(256), 0, cur_stream(),
                      (const u16*)qkv.data_ptr(), qwf.data_ptr<float>(),
                      kwf.data_ptr<float>(), sf.data_ptr<float>(), cf.data_ptr<float>(),
                      (u16*)q.data_ptr(), (u16*)k.data_ptr(), (u16*)v.data_ptr(),
@@ -137,7 +201,7 @@ std::vector<torch::Tensor> qkv_prep_bwd(torch::Tensor dq, torch::Tensor dk,
   auto dqw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
   auto dkw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
   size_t smem = 4 * 2 * C * sizeof(float);  // [waves = 256/64][2][C]
-  hipLaunchKernelGGL(qkv_prep_bwd_kernel, dim3(nblocks), dim3(256), smem, cur_stream(),
+  hipLaunchKernelGGL(qkv_prep_bwd_kernel<true>, dim3(nblocks), dim3(256), smem, cur_stream(),
                      (const u16*)dq.data_ptr(), (const u16*)dk.data_ptr(),
                      (const u16*)dv.data_ptr(), (const u16*)qkv.data_ptr(),
                      qwf.data_ptr<float>(), kwf.data_ptr<float>(),
@@ -149,6 +213,93 @@ std::vector<torch::Tensor> qkv_prep_bwd(torch::Tensor dq, torch::Tensor dk,
   auto dqw = dqw_p.sum(0).to(qw.scalar_type());
   auto dkw = dkw_p.sum(0).to(kw.scalar_type());
   return {dqkv, dqw, dkw};
+}
+
+// Q/K-only variants: no V copy in either direction. The backward fills slots
+// 0 and 1 of a caller-supplied dqkv (slot 2 is written by attn_bwd_packed).
+std::vector<torch::Tensor> qk_prep_fwd(torch::Tensor qkv, torch::Tensor qw,
+                                       torch::Tensor kw, torch::Tensor sin_t,
+                                       torch::Tensor cos_t, double eps) {
+  CHECK_GPU(qkv);
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "qkv must be bf16");
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "qk_prep_fwd: qkv must be (B,T,3,H,C)");
+  int B = qkv.size(0), T = qkv.size(1), H = qkv.size(3), C = qkv.size(4);
+  check_qkv_head_dim(C);
+  TORCH_CHECK(qw.numel() == C && kw.numel() == C, "qk_prep_fwd: weights must be (C,)");
+  TORCH_CHECK(sin_t.numel() == (long)T * (C / 2) && cos_t.numel() == sin_t.numel(),
+              "qk_prep_fwd: sin/cos must be (T, C/2)");
+  auto opt = qkv.options();
+  auto q = torch::empty({B, H, T, C}, opt);
+  auto k = torch::empty({B, H, T, C}, opt);
+  auto qstats = torch::empty({B, H, T, 2}, opt.dtype(torch::kFloat));
+  auto kstats = torch::empty({B, H, T, 2}, opt.dtype(torch::kFloat));
+  auto qwf = qw.to(torch::kFloat).contiguous();
+  auto kwf = kw.to(torch::kFloat).contiguous();
+  auto sf = sin_t.to(torch::kFloat).contiguous();
+  auto cf = cos_t.to(torch::kFloat).contiguous();
+  long nrows = (long)B * T * H * 2;
+  long grid = std::min((nrows + 3) / 4, (long)16384);
+  if (nrows > 0)
+    hipLaunchKernelGGL(qkv_prep_fwd_kernel<2>, dim3(grid), dim3(256), 0, cur_stream(),
+                       (const u16*)qkv.data_ptr(), qwf.data_ptr<float>(),
+                       kwf.data_ptr<float>(), sf.data_ptr<float>(), cf.data_ptr<float>(),
+                       (u16*)q.data_ptr(), (u16*)k.data_ptr(), (u16*)nullptr,
+                       qstats.data_ptr<float>(), kstats.data_ptr<float>(),
+                       B, T, H, C, (float)eps);
+  launch_check();
+  return {q, k, qstats, kstats};
+}
+
+std::vector<torch::Tensor> qk_prep_bwd(torch::Tensor dq, torch::Tensor dk,
+                                       torch::Tensor qkv, torch::Tensor qw,
+                                       torch::Tensor kw, torch::Tensor sin_t,
+                                       torch::Tensor cos_t, torch::Tensor qstats,
+                                       torch::Tensor kstats, torch::Tensor dqkv) {
+  CHECK_GPU(dq); CHECK_GPU(dk); CHECK_GPU(qkv); CHECK_GPU(dqkv);
+  CHECK_GPU(qstats); CHECK_GPU(kstats);
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16 &&
+              dq.scalar_type() == torch::kBFloat16 &&
+              dk.scalar_type() == torch::kBFloat16 &&
+              dqkv.scalar_type() == torch::kBFloat16,
+              "qk_prep_bwd: qkv, dq, dk, dqkv must be bf16");
+  TORCH_CHECK(qstats.scalar_type() == torch::kFloat &&
+              kstats.scalar_type() == torch::kFloat,
+              "qk_prep_bwd: stats must be fp32");
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "qk_prep_bwd: qkv must be (B,T,3,H,C)");
+  TORCH_CHECK(dqkv.sizes() == qkv.sizes(), "qk_prep_bwd: dqkv must have qkv's shape");
+  int B = qkv.size(0), T = qkv.size(1), H = qkv.size(3), C = qkv.size(4);
+  check_qkv_head_dim(C);
+  TORCH_CHECK(dq.numel() == (long)B * H * T * C && dk.numel() == dq.numel() &&
+              qstats.numel() == (long)B * H * T * 2 &&
+              kstats.numel() == qstats.numel(),
+              "qk_prep_bwd: dq/dk must be (B,H,T,C) and stats (B,H,T,2)");
+  TORCH_CHECK(qw.numel() == C && kw.numel() == C, "qk_prep_bwd: weights must be (C,)");
+  TORCH_CHECK(sin_t.numel() == (long)T * (C / 2) && cos_t.numel() == sin_t.numel(),
+              "qk_prep_bwd: sin/cos must be (T, C/2)");
+  auto qwf = qw.to(torch::kFloat).contiguous();
+  auto kwf = kw.to(torch::kFloat).contiguous();
+  auto sf = sin_t.to(torch::kFloat).contiguous();
+  auto cf = cos_t.to(torch::kFloat).contiguous();
+  // Same row sequence and grid as qkv_prep_bwd (V rows skipped): that keeps
+  // the partial sums, hence dqw and dkw, bit-identical to it.
+  long nrows = (long)B * T * H * 3;
+  int nblocks = (int)std::min((nrows + 3) / 4, (long)4096);
+  auto dqw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
+  auto dkw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
+  size_t smem = 4 * 2 * C * sizeof(float);  // [waves = 256/64][2][C]
+  if (nrows > 0)
+    hipLaunchKernelGGL(qkv_prep_bwd_kernel<false>, dim3(nblocks), dim3(256), smem,
+                       cur_stream(), (const u16*)dq.data_ptr(), (const u16*)dk.data_ptr(),
+                       (const u16*)nullptr, (const u16*)qkv.data_ptr(),
+                       qwf.data_ptr<float>(), kwf.data_ptr<float>(),
+                       sf.data_ptr<float>(), cf.data_ptr<float>(),
+                       qstats.data_ptr<float>(), kstats.data_ptr<float>(),
+                       (u16*)dqkv.data_ptr(), dqw_p.data_ptr<float>(),
+                       dkw_p.data_ptr<float>(), B, T, H, C);
+  launch_check();
+  auto dqw = dqw_p.sum(0).to(qw.scalar_type());
+  auto dkw = dkw_p.sum(0).to(kw.scalar_type());
+  return {dqw, dkw};
 }
 
 // ---------------------------------------------------------------------------
@@ -206,14 +357,49 @@ void adamw_step(torch::Tensor master, torch::Tensor grad, torch::Tensor m,
 }
 
 // ---------------------------------------------------------------------------
-std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v) {
-  CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v);
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn: bf16 required");
+// Strides (elements) of the three layouts the attention kernels address.
+static AttnStrides strides_bhtc(int H, int T, int C) {   // (B,H,T,C)
+  return {(long)H * T * C, (long)T * C, C};
+}
+static AttnStrides strides_bthc(int H, int T, int C) {   // (B,T,H,C)
+  return {(long)T * H * C, (long)C, H * C};
+}
+static AttnStrides strides_qkv_slot(int H, int T, int C) {  // one slot of (B,T,3,H,C)
+  return {(long)T * 3 * H * C, (long)C, 3 * H * C};
+}
+
+static void check_attn_qk(const torch::Tensor& q, const torch::Tensor& k) {
+  CHECK_GPU(q); CHECK_GPU(k);
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
+              k.scalar_type() == torch::kBFloat16, "attn: bf16 required");
+  TORCH_CHECK(q.dim() == 4 && k.sizes() == q.sizes(), "attn: q, k must be (B,H,T,C)");
+  TORCH_CHECK(q.size(2) % 128 == 0, "attn: T % 128 == 0 required (got ", q.size(2), ")");
+  TORCH_CHECK(q.size(3) == 64 || q.size(3) == 128,
+              "attn: head dim 64 or 128 (got ", q.size(3), ")");
+}
+// qkv (B,T,3,H,C) that q, k (B,H,T,C) were made from.
+static void check_attn_packed(const torch::Tensor& q, const torch::Tensor& qkv,
+                              const char* name) {
+  CHECK_GPU(qkv);
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "attn: ", name, " must be bf16");
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(0) == q.size(0) && qkv.size(1) == q.size(2) &&
+              qkv.size(2) == 3 && qkv.size(3) == q.size(1) && qkv.size(4) == q.size(3),
+              "attn: ", name, " must be (B,T,3,H,C) matching q (B,H,T,C)");
+}
+static void check_attn_bthc(const torch::Tensor& q, const torch::Tensor& x,
+                            const char* name) {
+  CHECK_GPU(x);
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "attn: ", name, " must be bf16");
+  TORCH_CHECK(x.dim() == 4 && x.size(0) == q.size(0) && x.size(1) == q.size(2) &&
+              x.size(2) == q.size(1) && x.size(3) == q.size(3),
+              "attn: ", name, " must be (B,T,H,C) matching q (B,H,T,C)");
+}
+
+// One launcher for every layout: v is read and o written through strides.
+static void attn_fwd_launch(torch::Tensor q, torch::Tensor k, const u16* vp,
+                            AttnStrides sv, u16* op, AttnStrides so,
+                            torch::Tensor lse) {
   int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
-  TORCH_CHECK(T % 128 == 0, "attn: T % 128 == 0 required (got ", T, ")");
-  TORCH_CHECK(C == 64 || C == 128, "attn: head dim 64 or 128 (got ", C, ")");
-  auto o = torch::empty_like(q);
-  auto lse = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
   // Measured best: 8-wave WGs at 2 waves/SIMD, SPW=1. The SPW=2
   // mirrored-strip variant (1 wave/SIMD for C=128) and 3-waves/SIMD were
   // both measured slower — SQ_WAIT is memory-wait dominated, so wave
@@ -226,8 +412,8 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
   hipLaunchKernelGGL((attn_fwd_kernel<CC, NN, SS, MM>), dim3(grid),             \
                      dim3(NN * 64),                                             \
                      smem, cur_stream(), (const u16*)q.data_ptr(),              \
-                     (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),        \
-                     (u16*)o.data_ptr(), lse.data_ptr<float>(), B, H, T)
+                     (const u16*)k.data_ptr(), vp,        \
+                     op, lse.data_ptr<float>(), B, H, T, sv, so)
   // depth-2 prefetch single-tile kernel (4 LDS buffers, loads 2 tiles
   // ahead): opt-in A/B via MIDGPT_ATTN_FWD_D2=1
   static const bool fwd_d2 = getenv("MIDGPT_ATTN_FWD_D2") != nullptr;
@@ -236,15 +422,15 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
     if (C == 128)
       hipLaunchKernelGGL((attn_fwd_d2_kernel<128, 8>), dim3(grid), dim3(512),
                          smem_d2, cur_stream(), (const u16*)q.data_ptr(),
-                         (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),
-                         (u16*)o.data_ptr(), lse.data_ptr<float>(), B, H, T);
+                         (const u16*)k.data_ptr(), vp,
+                         op, lse.data_ptr<float>(), B, H, T, sv, so);
     else
       hipLaunchKernelGGL((attn_fwd_d2_kernel<64, 8>), dim3(grid), dim3(512),
                          smem_d2, cur_stream(), (const u16*)q.data_ptr(),
-                         (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),
-                         (u16*)o.data_ptr(), lse.data_ptr<float>(), B, H, T);
+                         (const u16*)k.data_ptr(), vp,
+                         op, lse.data_ptr<float>(), B, H, T, sv, so);
     launch_check();
-    return {o, lse};
+    return;
   }
   // paired-tile kernel (one merged rescale per 64 k): measured +4% at
   // C=128, -4% at C=64 -> default for C=128 only (MIDGPT_ATTN_FWD2=1
@@ -262,13 +448,13 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);            \
       hipLaunchKernelGGL((attn_fwd2_kernel<CC, 8>), dim3(grid), dim3(512),      \
                          smem2, cur_stream(), (const u16*)q.data_ptr(),         \
-                         (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),    \
-                         (u16*)o.data_ptr(), lse.data_ptr<float>(), B, H, T);   \
+                         (const u16*)k.data_ptr(), vp,    \
+                         op, lse.data_ptr<float>(), B, H, T, sv, so);   \
     } while (0)
     if (C == 128) LAUNCH_FWD2(128); else LAUNCH_FWD2(64);
 #undef LAUNCH_FWD2
     launch_check();
-    return {o, lse};
+    return;
   }
   static const bool minw3 = getenv("MIDGPT_ATTN_FWD_MINW3") != nullptr;
   if (C == 128 && NW == 8 && minw3) LAUNCH_FWD(128, 8, 1, 3);
@@ -279,23 +465,44 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
   else LAUNCH_FWD(64, 4, 1, 2);
 #undef LAUNCH_FWD
   launch_check();
+  return;
+}
+
+std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v) {
+  CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v);
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn: bf16 required");
+  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
+  TORCH_CHECK(T % 128 == 0, "attn: T % 128 == 0 required (got ", T, ")");
+  TORCH_CHECK(C == 64 || C == 128, "attn: head dim 64 or 128 (got ", C, ")");
+  auto o = torch::empty_like(q);
+  auto lse = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
+  const AttnStrides st = strides_bhtc(H, T, C);
+  attn_fwd_launch(q, k, (const u16*)v.data_ptr(), st, (u16*)o.data_ptr(), st, lse);
   return {o, lse};
 }
 
-std::vector<torch::Tensor> attn_bwd(torch::Tensor dO, torch::Tensor q, torch::Tensor k,
-                                    torch::Tensor v, torch::Tensor o, torch::Tensor lse) {
-  CHECK_GPU(dO); CHECK_GPU(q);
+// One launcher for every layout: dO, v, o are read and dv written through
+// strides. Returns {dq, dk} (packed (B,H,T,C)).
+static std::vector<torch::Tensor> attn_bwd_launch(
+    const u16* dop, AttnStrides sdo, torch::Tensor q, torch::Tensor k,
+    const u16* vp, AttnStrides sv, const u16* op, AttnStrides so,
+    torch::Tensor lse, u16* dvp, AttnStrides sdv, u16* do_copy = nullptr) {
   int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
   long N = (long)B * H * T;
   auto delta = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
+  TORCH_CHECK(N < (1L << 31), "attn: B*H*T must be below 2^31");
   long dgrid = std::min((N + 3) / 4, (long)8192);
   hipLaunchKernelGGL(attn_delta_kernel, dim3(dgrid), dim3(256), 0, cur_stream(),
-                     (const u16*)dO.data_ptr(), (const u16*)o.data_ptr(),
-                     delta.data_ptr<float>(), N, C);
+                     dop, op,
+                     delta.data_ptr<float>(), N, C, H, T, sdo, so, do_copy,
+                     (int)(sdo.h < sdo.r));
   launch_check();
+  if (do_copy) {  // the delta kernel left dO as packed (B,H,T,C) there
+    dop = do_copy;
+    sdo = strides_bhtc(H, T, C);
+  }
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
-  auto dv = torch::empty_like(v);
   static const bool dkv4 = getenv("MIDGPT_ATTN_DKV_NW4") != nullptr;
   const int NW_A = dkv4 ? 4 : ((T % 256 == 0) ? 8 : 4);  // dkv geometry
   const int NW_B = NW_A;                     // dq geometry
@@ -323,51 +530,51 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dO, torch::Tensor q, torch::Te
     if (abl && abl[0] == '1')                                                   \
       hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NA, 1>), dim3(grid_a),        \
                          dim3(NA * 64), smem_a, cur_stream(),                   \
-                         (const u16*)dO.data_ptr(), (const u16*)q.data_ptr(),   \
-                         (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),    \
+                         dop, (const u16*)q.data_ptr(),   \
+                         (const u16*)k.data_ptr(), vp,    \
                          lse.data_ptr<float>(), delta.data_ptr<float>(),        \
-                         (u16*)dk.data_ptr(), (u16*)dv.data_ptr(), B, H, T);    \
+                         (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);    \
     else if (abl && abl[0] == '3')                                              \
       hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NA, 3>), dim3(grid_a),        \
                          dim3(NA * 64), smem_a, cur_stream(),                   \
-                         (const u16*)dO.data_ptr(), (const u16*)q.data_ptr(),   \
-                         (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),    \
+                         dop, (const u16*)q.data_ptr(),   \
+                         (const u16*)k.data_ptr(), vp,    \
                          lse.data_ptr<float>(), delta.data_ptr<float>(),        \
-                         (u16*)dk.data_ptr(), (u16*)dv.data_ptr(), B, H, T);    \
+                         (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);    \
     else if (abl && abl[0] == '4')                                              \
       hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NA, 4>), dim3(grid_a),        \
                          dim3(NA * 64), smem_a, cur_stream(),                   \
-                         (const u16*)dO.data_ptr(), (const u16*)q.data_ptr(),   \
-                         (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),    \
+                         dop, (const u16*)q.data_ptr(),   \
+                         (const u16*)k.data_ptr(), vp,    \
                          lse.data_ptr<float>(), delta.data_ptr<float>(),        \
-                         (u16*)dk.data_ptr(), (u16*)dv.data_ptr(), B, H, T);    \
+                         (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);    \
     else if (abl && abl[0] == '5')                                              \
       hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NA, 5>), dim3(grid_a),        \
                          dim3(NA * 64), smem_a, cur_stream(),                   \
-                         (const u16*)dO.data_ptr(), (const u16*)q.data_ptr(),   \
-                         (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),    \
+                         dop, (const u16*)q.data_ptr(),   \
+                         (const u16*)k.data_ptr(), vp,    \
                          lse.data_ptr<float>(), delta.data_ptr<float>(),        \
-                         (u16*)dk.data_ptr(), (u16*)dv.data_ptr(), B, H, T);    \
+                         (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);    \
     else if (abl && abl[0] == '2')                                              \
       hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NA, 2>), dim3(grid_a),        \
                          dim3(NA * 64), smem_a, cur_stream(),                   \
-                         (const u16*)dO.data_ptr(), (const u16*)q.data_ptr(),   \
-                         (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),    \
+                         dop, (const u16*)q.data_ptr(),   \
+                         (const u16*)k.data_ptr(), vp,    \
                          lse.data_ptr<float>(), delta.data_ptr<float>(),        \
-                         (u16*)dk.data_ptr(), (u16*)dv.data_ptr(), B, H, T);    \
+                         (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);    \
     else                                                                        \
       hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NA, 0>), dim3(grid_a),        \
                          dim3(NA * 64), smem_a, cur_stream(),                   \
-                         (const u16*)dO.data_ptr(), (const u16*)q.data_ptr(),   \
-                         (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),    \
+                         dop, (const u16*)q.data_ptr(),   \
+                         (const u16*)k.data_ptr(), vp,    \
                          lse.data_ptr<float>(), delta.data_ptr<float>(),        \
-                         (u16*)dk.data_ptr(), (u16*)dv.data_ptr(), B, H, T);    \
+                         (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);    \
     hipLaunchKernelGGL((attn_bwd_dq_kernel<CC, NB, SS, MM>), dim3(grid_b),      \
                        dim3(NB * 64),                                           \
-                       smem_b, cur_stream(), (const u16*)dO.data_ptr(),         \
+                       smem_b, cur_stream(), dop,         \
                        (const u16*)q.data_ptr(), (const u16*)k.data_ptr(),      \
-                       (const u16*)v.data_ptr(), lse.data_ptr<float>(),         \
-                       delta.data_ptr<float>(), (u16*)dq.data_ptr(), B, H, T);  \
+                       vp, lse.data_ptr<float>(),         \
+                       delta.data_ptr<float>(), (u16*)dq.data_ptr(), B, H, T, sdo, sv);  \
   } while (0)
   static const bool bwd_minw3 = getenv("MIDGPT_ATTN_BWD_MINW3") != nullptr;
   if (C == 64 && NW_A == 8 && bwd_minw3 && !getenv("MIDGPT_DKV_ABLATE")) {
@@ -379,18 +586,18 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dO, torch::Tensor q, torch::Te
           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_a);
     hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, 8, 0, 3>), dim3(grid_a),
                        dim3(512), smem_a, cur_stream(),
-                       (const u16*)dO.data_ptr(), (const u16*)q.data_ptr(),
-                       (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),
+                       dop, (const u16*)q.data_ptr(),
+                       (const u16*)k.data_ptr(), vp,
                        lse.data_ptr<float>(), delta.data_ptr<float>(),
-                       (u16*)dk.data_ptr(), (u16*)dv.data_ptr(), B, H, T);
+                       (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);
     hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 8, 1, 3>), dim3(grid_b),
                        dim3(512), smem_b, cur_stream(),
-                       (const u16*)dO.data_ptr(), (const u16*)q.data_ptr(),
-                       (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),
+                       dop, (const u16*)q.data_ptr(),
+                       (const u16*)k.data_ptr(), vp,
                        lse.data_ptr<float>(), delta.data_ptr<float>(),
-                       (u16*)dq.data_ptr(), B, H, T);
+                       (u16*)dq.data_ptr(), B, H, T, sdo, sv);
     launch_check();
-    return {dq, dk, dv};
+    return {dq, dk};
   }
   if (C == 128 && NW_A == 8) LAUNCH_BWD(128, 8, 8, 1, 2);
   else if (C == 128) LAUNCH_BWD(128, 4, 4, 1, 2);
@@ -398,7 +605,19 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dO, torch::Tensor q, torch::Te
   else LAUNCH_BWD(64, 4, 4, 1, 2);
 #undef LAUNCH_BWD
   launch_check();
-  return {dq, dk, dv};
+  return {dq, dk};
+}
+
+std::vector<torch::Tensor> attn_bwd(torch::Tensor dO, torch::Tensor q, torch::Tensor k,
+                                    torch::Tensor v, torch::Tensor o, torch::Tensor lse) {
+  CHECK_GPU(dO); CHECK_GPU(q);
+  int H = q.size(1), T = q.size(2), C = q.size(3);
+  auto dv = torch::empty_like(v);
+  const AttnStrides st = strides_bhtc(H, T, C);
+  auto r = attn_bwd_launch((const u16*)dO.data_ptr(), st, q, k,
+                           (const u16*)v.data_ptr(), st, (const u16*)o.data_ptr(), st,
+                           lse, (u16*)dv.data_ptr(), st);
+  return {r[0], r[1], dv};
 }
 
 // ---------------------------------------------------------------------------
@@ -416,6 +635,29 @@ static DropArgs drop_args(double p, int64_t seed) {
           (float)(1.0 / (1.0 - p))};
 }
 
+static void attn_fwd_dropout_launch(torch::Tensor q, torch::Tensor k, const u16* vp,
+                                    AttnStrides sv, u16* op, AttnStrides so,
+                                    torch::Tensor lse, const DropArgs& d) {
+  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
+  const int NW = (T % 256 == 0) ? 8 : 4;
+  long grid = (long)B * H * (T / (NW * 32));
+  size_t smem = std::max((size_t)(4 * 32 * C * 2), (size_t)(NW * 32 * 32 * 4));
+#define LAUNCH_FWD_DROP(CC, NN)                                                 \
+  hipLaunchKernelGGL((attn_fwd_kernel<CC, NN, 1, 2, true>), dim3(grid),         \
+                     dim3(NN * 64), smem, cur_stream(),                         \
+                     (const u16*)q.data_ptr(), (const u16*)k.data_ptr(),        \
+                     vp, op,              \
+                     lse.data_ptr<float>(), B, H, T, sv, so, d.seed_lo, d.seed_hi,      \
+                     d.thr, d.inv_keep)
+  if (C == 128 && NW == 8) LAUNCH_FWD_DROP(128, 8);
+  else if (C == 128) LAUNCH_FWD_DROP(128, 4);
+  else if (NW == 8) LAUNCH_FWD_DROP(64, 8);
+  else LAUNCH_FWD_DROP(64, 4);
+#undef LAUNCH_FWD_DROP
+  launch_check();
+  return;
+}
+
 std::vector<torch::Tensor> attn_fwd_dropout(torch::Tensor q, torch::Tensor k,
                                             torch::Tensor v, double p, int64_t seed) {
   CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v);
@@ -426,45 +668,33 @@ std::vector<torch::Tensor> attn_fwd_dropout(torch::Tensor q, torch::Tensor k,
   const DropArgs d = drop_args(p, seed);
   auto o = torch::empty_like(q);
   auto lse = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
-  const int NW = (T % 256 == 0) ? 8 : 4;
-  long grid = (long)B * H * (T / (NW * 32));
-  size_t smem = std::max((size_t)(4 * 32 * C * 2), (size_t)(NW * 32 * 32 * 4));
-#define LAUNCH_FWD_DROP(CC, NN)                                                 \
-  hipLaunchKernelGGL((attn_fwd_kernel<CC, NN, 1, 2, true>), dim3(grid),         \
-                     dim3(NN * 64), smem, cur_stream(),                         \
-                     (const u16*)q.data_ptr(), (const u16*)k.data_ptr(),        \
-                     (const u16*)v.data_ptr(), (u16*)o.data_ptr(),              \
-                     lse.data_ptr<float>(), B, H, T, d.seed_lo, d.seed_hi,      \
-                     d.thr, d.inv_keep)
-  if (C == 128 && NW == 8) LAUNCH_FWD_DROP(128, 8);
-  else if (C == 128) LAUNCH_FWD_DROP(128, 4);
-  else if (NW == 8) LAUNCH_FWD_DROP(64, 8);
-  else LAUNCH_FWD_DROP(64, 4);
-#undef LAUNCH_FWD_DROP
-  launch_check();
+  const AttnStrides st = strides_bhtc(H, T, C);
+  attn_fwd_dropout_launch(q, k, (const u16*)v.data_ptr(), st, (u16*)o.data_ptr(), st,
+                          lse, d);
   return {o, lse};
 }
 
-std::vector<torch::Tensor> attn_bwd_dropout(torch::Tensor dO, torch::Tensor q,
-                                            torch::Tensor k, torch::Tensor v,
-                                            torch::Tensor o, torch::Tensor lse,
-                                            double p, int64_t seed) {
-  CHECK_GPU(dO); CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v); CHECK_GPU(o); CHECK_GPU(lse);
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn: bf16 required");
+static std::vector<torch::Tensor> attn_bwd_dropout_launch(
+    const u16* dop, AttnStrides sdo, torch::Tensor q, torch::Tensor k,
+    const u16* vp, AttnStrides sv, const u16* op, AttnStrides so,
+    torch::Tensor lse, u16* dvp, AttnStrides sdv, const DropArgs& d,
+    u16* do_copy = nullptr) {
   int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
-  TORCH_CHECK(T % 128 == 0, "attn: T % 128 == 0 required (got ", T, ")");
-  TORCH_CHECK(C == 64 || C == 128, "attn: head dim 64 or 128 (got ", C, ")");
-  const DropArgs d = drop_args(p, seed);
   long N = (long)B * H * T;
   auto delta = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
+  TORCH_CHECK(N < (1L << 31), "attn: B*H*T must be below 2^31");
   long dgrid = std::min((N + 3) / 4, (long)8192);
   hipLaunchKernelGGL(attn_delta_kernel, dim3(dgrid), dim3(256), 0, cur_stream(),
-                     (const u16*)dO.data_ptr(), (const u16*)o.data_ptr(),
-                     delta.data_ptr<float>(), N, C);
+                     dop, op,
+                     delta.data_ptr<float>(), N, C, H, T, sdo, so, do_copy,
+                     (int)(sdo.h < sdo.r));
   launch_check();
+  if (do_copy) {  // the delta kernel left dO as packed (B,H,T,C) there
+    dop = do_copy;
+    sdo = strides_bhtc(H, T, C);
+  }
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
-  auto dv = torch::empty_like(v);
   const int NW = (T % 256 == 0) ? 8 : 4;
   long grid = (long)B * H * (T / (NW * 32));
   size_t smem_a = std::max((size_t)(2 * 4 * 32 * C) * 2 + 2 * 64 * 4,
@@ -485,17 +715,17 @@ std::vector<torch::Tensor> attn_bwd_dropout(torch::Tensor dO, torch::Tensor q,
                           (int)smem_b);                                         \
     hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NN, 0, 2, true>), dim3(grid),   \
                        dim3(NN * 64), smem_a, cur_stream(),                     \
-                       (const u16*)dO.data_ptr(), (const u16*)q.data_ptr(),     \
-                       (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),      \
+                       dop, (const u16*)q.data_ptr(),     \
+                       (const u16*)k.data_ptr(), vp,      \
                        lse.data_ptr<float>(), delta.data_ptr<float>(),          \
-                       (u16*)dk.data_ptr(), (u16*)dv.data_ptr(), B, H, T,       \
-                       d.seed_lo, d.seed_hi, d.thr, d.inv_keep);                \
+                       (u16*)dk.data_ptr(), dvp, B, H, T,       \
+                       sdo, sv, sdv, d.seed_lo, d.seed_hi, d.thr, d.inv_keep);                \
     hipLaunchKernelGGL((attn_bwd_dq_kernel<CC, NN, 1, 2, true>), dim3(grid),    \
                        dim3(NN * 64), smem_b, cur_stream(),                     \
-                       (const u16*)dO.data_ptr(), (const u16*)q.data_ptr(),     \
-                       (const u16*)k.data_ptr(), (const u16*)v.data_ptr(),      \
+                       dop, (const u16*)q.data_ptr(),     \
+                       (const u16*)k.data_ptr(), vp,      \
                        lse.data_ptr<float>(), delta.data_ptr<float>(),          \
-                       (u16*)dq.data_ptr(), B, H, T, d.seed_lo, d.seed_hi,      \
+                       (u16*)dq.data_ptr(), B, H, T, sdo, sv, d.seed_lo, d.seed_hi,      \
                        d.thr, d.inv_keep);                                      \
   } while (0)
   if (C == 128 && NW == 8) LAUNCH_BWD_DROP(128, 8);
@@ -504,7 +734,96 @@ std::vector<torch::Tensor> attn_bwd_dropout(torch::Tensor dO, torch::Tensor q,
   else LAUNCH_BWD_DROP(64, 4);
 #undef LAUNCH_BWD_DROP
   launch_check();
-  return {dq, dk, dv};
+  return {dq, dk};
+}
+
+std::vector<torch::Tensor> attn_bwd_dropout(torch::Tensor dO, torch::Tensor q,
+                                            torch::Tensor k, torch::Tensor v,
+                                            torch::Tensor o, torch::Tensor lse,
+                                            double p, int64_t seed) {
+  CHECK_GPU(dO); CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v); CHECK_GPU(o); CHECK_GPU(lse);
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn: bf16 required");
+  int H = q.size(1), T = q.size(2), C = q.size(3);
+  TORCH_CHECK(T % 128 == 0, "attn: T % 128 == 0 required (got ", T, ")");
+  TORCH_CHECK(C == 64 || C == 128, "attn: head dim 64 or 128 (got ", C, ")");
+  const DropArgs d = drop_args(p, seed);
+  auto dv = torch::empty_like(v);
+  const AttnStrides st = strides_bhtc(H, T, C);
+  auto r = attn_bwd_dropout_launch((const u16*)dO.data_ptr(), st, q, k,
+                                   (const u16*)v.data_ptr(), st,
+                                   (const u16*)o.data_ptr(), st, lse,
+                                   (u16*)dv.data_ptr(), st, d);
+  return {r[0], r[1], dv};
+}
+
+// ---------------------------------------------------------------------------
+// Copy-free layouts around attention: o and dO are (B,T,H,C) (what the output
+// projection reads and what its backward hands back) and dV goes straight into
+// slot 2 of a caller-supplied (B,T,3,H,C) dqkv. v is either the (B,H,T,C)
+// copy or the packed (B,T,3,H,C) projection itself, read in place from slot 2.
+// p == 0: no dropout.
+static const u16* packed_or_plain_v(const torch::Tensor& q, const torch::Tensor& v,
+                                    AttnStrides* sv) {
+  int H = q.size(1), T = q.size(2), C = q.size(3);
+  if (v.dim() == 5) {
+    check_attn_packed(q, v, "qkv");
+    *sv = strides_qkv_slot(H, T, C);
+    return (const u16*)v.data_ptr() + 2L * H * C;
+  }
+  CHECK_GPU(v);
+  TORCH_CHECK(v.scalar_type() == torch::kBFloat16 && v.sizes() == q.sizes(),
+              "attn: v must be bf16 (B,H,T,C) like q, or the packed (B,T,3,H,C) qkv");
+  *sv = strides_bhtc(H, T, C);
+  return (const u16*)v.data_ptr();
+}
+
+std::vector<torch::Tensor> attn_fwd_packed(torch::Tensor q, torch::Tensor k,
+                                           torch::Tensor v, double p, int64_t seed) {
+  check_attn_qk(q, k);
+  AttnStrides sv;
+  const u16* vp = packed_or_plain_v(q, v, &sv);
+  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
+  auto o = torch::empty({B, T, H, C}, q.options());
+  auto lse = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
+  const AttnStrides so = strides_bthc(H, T, C);
+  if (p > 0.0)
+    attn_fwd_dropout_launch(q, k, vp, sv, (u16*)o.data_ptr(), so, lse, drop_args(p, seed));
+  else
+    attn_fwd_launch(q, k, vp, sv, (u16*)o.data_ptr(), so, lse);
+  return {o, lse};
+}
+
+// stage_do: the delta kernel, which reads dO anyway, also writes it out as
+// (B,H,T,C) for the dkv and dq kernels; false: they read (B,T,H,C) in place.
+std::vector<torch::Tensor> attn_bwd_packed(torch::Tensor dO, torch::Tensor q,
+                                           torch::Tensor k, torch::Tensor v,
+                                           torch::Tensor o, torch::Tensor lse,
+                                           torch::Tensor dqkv, double p, int64_t seed,
+                                           bool stage_do) {
+  check_attn_qk(q, k);
+  AttnStrides sv;
+  const u16* vp = packed_or_plain_v(q, v, &sv);
+  check_attn_packed(q, dqkv, "dqkv");
+  check_attn_bthc(q, dO, "dO");
+  check_attn_bthc(q, o, "o");
+  CHECK_GPU(lse);
+  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
+  TORCH_CHECK(lse.scalar_type() == torch::kFloat && lse.numel() == (long)B * H * T,
+              "attn: lse must be fp32 (B,H,T)");
+  u16* dvp = (u16*)dqkv.data_ptr() + 2L * H * C;
+  const AttnStrides sdv = strides_qkv_slot(H, T, C), so = strides_bthc(H, T, C);
+  torch::Tensor do_copy;
+  u16* dcp = nullptr;
+  if (stage_do) {
+    do_copy = torch::empty_like(q);
+    dcp = (u16*)do_copy.data_ptr();
+  }
+  if (p > 0.0)
+    return attn_bwd_dropout_launch((const u16*)dO.data_ptr(), so, q, k, vp, sv,
+                                   (const u16*)o.data_ptr(), so, lse, dvp, sdv,
+                                   drop_args(p, seed), dcp);
+  return attn_bwd_launch((const u16*)dO.data_ptr(), so, q, k, vp, sv,
+                         (const u16*)o.data_ptr(), so, lse, dvp, sdv, dcp);
 }
 
 // ---------------------------------------------------------------------------
@@ -610,6 +929,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("rmsnorm_bwd", &rmsnorm_bwd);
   mod.def("qkv_prep_fwd", &qkv_prep_fwd);
   mod.def("qkv_prep_bwd", &qkv_prep_bwd);
+  mod.def("add_rmsnorm_fwd", &add_rmsnorm_fwd);
+  mod.def("add_rmsnorm_bwd", &add_rmsnorm_bwd);
+  mod.def("qk_prep_fwd", &qk_prep_fwd);
+  mod.def("qk_prep_bwd", &qk_prep_bwd);
   mod.def("ce_fwd", &ce_fwd);
   mod.def("ce_bwd", &ce_bwd);
   mod.def("adamw_step", &adamw_step);
@@ -617,6 +940,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("attn_bwd", &attn_bwd);
   mod.def("attn_fwd_dropout", &attn_fwd_dropout);
   mod.def("attn_bwd_dropout", &attn_bwd_dropout);
+  mod.def("attn_fwd_packed", &attn_fwd_packed, py::arg("q"), py::arg("k"),
+          py::arg("v"), py::arg("p") = 0.0, py::arg("seed") = 0);
+  mod.def("attn_bwd_packed", &attn_bwd_packed, py::arg("dO"), py::arg("q"),
+          py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"),
+          py::arg("dqkv"), py::arg("p") = 0.0, py::arg("seed") = 0,
+          py::arg("stage_do") = true);
   mod.def("embedding_bwd", &embedding_bwd);
   mod.def("gelu_fwd", &gelu_fwd);
   mod.def("gelu_bwd", &gelu_bwd);

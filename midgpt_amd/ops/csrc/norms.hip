@@ -32,6 +32,30 @@ DEVINL void store8(u16* p, const float* in) {
   *(u16x8*)p = v;
 }
 
+// ---- arithmetic shared by the plain and the fused (add +) RMSNorm kernels ----
+// The fused kernels must match the plain ones bit for bit, and where a product
+// feeds a sum, contracting the two into an FMA or not changes the last bit.
+// Left to the compiler that choice is made per expression and per kernel, so
+// both families call these helpers, which fix it with contraction off: the
+// reductions round every product before adding it; the backward's output is
+// fma(r, g, -(x * r3dot)), except for element 0 of each 8-vector, whose two
+// products are rounded and subtracted (how rmsnorm_bwd_bf16 has always been
+// compiled, kept so that its results do not move).
+DEVINL float acc_prod(float acc, float a, float b) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return acc + p;
+}
+DEVINL float rmsnorm_bwd_elem(int j, float r, float g, float x, float r3dot) {
+#pragma clang fp contract(off)
+  const float xr = x * r3dot;
+  if (j == 0) {
+    const float rg = r * g;
+    return rg - xr;
+  }
+  return __builtin_fmaf(r, g, -xr);
+}
+
 // bf16, D % 8 == 0 (all model dims). Vectorized u16x8 loads (guide G13).
 __global__ void rmsnorm_fwd_bf16(const u16* __restrict__ x, const float* __restrict__ w,
                                  u16* __restrict__ y, float* __restrict__ invrms,
@@ -46,7 +70,7 @@ __global__ void rmsnorm_fwd_bf16(const u16* __restrict__ x, const float* __restr
     for (int i = lane * 8; i < D; i += WAVE * 8) {
       load8(xr + i, buf);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) ss += buf[j] * buf[j];
+      for (int j = 0; j < 8; ++j) ss = acc_prod(ss, buf[j], buf[j]);
     }
     ss = group_sum<WAVE>(ss);
     float r = rsqrtf(ss / D + eps);
@@ -113,7 +137,7 @@ __global__ void rmsnorm_bwd_bf16(const u16* __restrict__ dy, const u16* __restri
       load8(dyr + i, gb);
       load8(xr + i, xb);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) dot += gb[j] * xb[j];
+      for (int j = 0; j < 8; ++j) dot = acc_prod(dot, gb[j], xb[j]);
     }
     dot = group_sum<WAVE>(dot) / D;
     const float r3dot = r * r * r * dot;
@@ -122,8 +146,166 @@ __global__ void rmsnorm_bwd_bf16(const u16* __restrict__ dy, const u16* __restri
       load8(dyr + i, gb);
       load8(xr + i, xb);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) gb[j] = r * gb[j] - xb[j] * r3dot;
+      for (int j = 0; j < 8; ++j) gb[j] = rmsnorm_bwd_elem(j, r, gb[j], xb[j], r3dot);
       store8(dxr + i, gb);
+    }
+  }
+}
+
+// ============================================================
+// Fused residual add + RMSNorm (bf16, weightless, D % 8 == 0).
+// Forward: s = bf16(x + r); y, invrms = rmsnorm(s) computed from the ROUNDED
+// s, i.e. exactly what an elementwise add followed by rmsnorm_fwd_bf16
+// gives, in 4 passes over the activation instead of 5. The per-lane and
+// cross-lane summation order is that of rmsnorm_fwd_bf16, so the results
+// are bit-identical to the two-kernel sequence.
+// NI > 0: the row (NI x 512 columns) stays in registers between the
+// reduction and the write; NI == 0: any D, s is re-read (L2-hot).
+// ============================================================
+template <int NI>
+__global__ void add_rmsnorm_fwd_bf16(const u16* __restrict__ x, const u16* __restrict__ r,
+                                     u16* __restrict__ s, u16* __restrict__ y,
+                                     float* __restrict__ invrms, long N, int D, float eps) {
+  const int lane = lane_id();
+  const long row0 = (long)blockIdx.x * (blockDim.x / WAVE) + wave_id();
+  const long rstep = (long)gridDim.x * (blockDim.x / WAVE);
+  for (long row = row0; row < N; row += rstep) {
+    const u16* xr = x + row * (long)D;
+    const u16* rr = r + row * (long)D;
+    u16* sr = s + row * (long)D;
+    u16* yr = y + row * (long)D;
+    float ss = 0.f;
+    float buf[8];
+    if constexpr (NI > 0) {
+      u16x8 sv[NI];
+#pragma unroll
+      for (int it = 0; it < NI; ++it) {
+        const int i = lane * 8 + it * WAVE * 8;
+        if (i < D) {
+          const u16x8 a = *(const u16x8*)(xr + i);
+          const u16x8 b = *(const u16x8*)(rr + i);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            sv[it][j] = f2b(b2f(a[j]) + b2f(b[j]));
+            buf[j] = b2f(sv[it][j]);
+          }
+#pragma unroll
+          for (int j = 0; j < 8; ++j) ss = acc_prod(ss, buf[j], buf[j]);
+          *(u16x8*)(sr + i) = sv[it];
+        }
+      }
+      ss = group_sum<WAVE>(ss);
+      const float rs = rsqrtf(ss / D + eps);
+      if (lane == 0) invrms[row] = rs;
+#pragma unroll
+      for (int it = 0; it < NI; ++it) {
+        const int i = lane * 8 + it * WAVE * 8;
+        if (i < D) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) buf[j] = b2f(sv[it][j]) * rs;
+          store8(yr + i, buf);
+        }
+      }
+    } else {
+      for (int i = lane * 8; i < D; i += WAVE * 8) {
+        const u16x8 a = *(const u16x8*)(xr + i);
+        const u16x8 b = *(const u16x8*)(rr + i);
+        u16x8 sv;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          sv[j] = f2b(b2f(a[j]) + b2f(b[j]));
+          buf[j] = b2f(sv[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ss = acc_prod(ss, buf[j], buf[j]);
+        *(u16x8*)(sr + i) = sv;
+      }
+      ss = group_sum<WAVE>(ss);
+      const float rs = rsqrtf(ss / D + eps);
+      if (lane == 0) invrms[row] = rs;
+      // each lane re-reads only the 16-byte chunks it wrote itself
+      for (int i = lane * 8; i < D; i += WAVE * 8) {
+        load8(sr + i, buf);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) buf[j] *= rs;
+        store8(yr + i, buf);
+      }
+    }
+  }
+}
+
+// Backward: dx = bf16(ds + bf16(rmsnorm_bwd(dy, s, invrms))); the inner
+// rounding makes it bit-identical to rmsnorm_bwd_bf16 followed by the
+// gradient-accumulation add, in 4 passes instead of 6. ds == nullptr: the
+// plain norm backward. dx is the gradient of both addends of s.
+template <int NI>
+__global__ void add_rmsnorm_bwd_bf16(const u16* __restrict__ ds, const u16* __restrict__ dy,
+                                     const u16* __restrict__ s,
+                                     const float* __restrict__ invrms,
+                                     u16* __restrict__ dx, long N, int D) {
+  const int lane = lane_id();
+  const long row0 = (long)blockIdx.x * (blockDim.x / WAVE) + wave_id();
+  const long rstep = (long)gridDim.x * (blockDim.x / WAVE);
+  for (long row = row0; row < N; row += rstep) {
+    const u16* dyr = dy + row * (long)D;
+    const u16* xr = s + row * (long)D;
+    const u16* dsr = ds ? ds + row * (long)D : nullptr;
+    u16* dxr = dx + row * (long)D;
+    const float r = invrms[row];
+    float dot = 0.f;
+    float gb[8], xb[8];
+    if constexpr (NI > 0) {
+      u16x8 gv[NI], xv[NI];
+#pragma unroll
+      for (int it = 0; it < NI; ++it) {
+        const int i = lane * 8 + it * WAVE * 8;
+        if (i < D) {
+          gv[it] = *(const u16x8*)(dyr + i);
+          xv[it] = *(const u16x8*)(xr + i);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) dot = acc_prod(dot, b2f(gv[it][j]), b2f(xv[it][j]));
+        }
+      }
+      dot = group_sum<WAVE>(dot) / D;
+      const float r3dot = r * r * r * dot;
+#pragma unroll
+      for (int it = 0; it < NI; ++it) {
+        const int i = lane * 8 + it * WAVE * 8;
+        if (i < D) {
+          u16x8 out;
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            out[j] = f2b(rmsnorm_bwd_elem(j, r, b2f(gv[it][j]), b2f(xv[it][j]), r3dot));
+          if (dsr) {
+            const u16x8 a = *(const u16x8*)(dsr + i);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) out[j] = f2b(b2f(a[j]) + b2f(out[j]));
+          }
+          *(u16x8*)(dxr + i) = out;
+        }
+      }
+    } else {
+      for (int i = lane * 8; i < D; i += WAVE * 8) {
+        load8(dyr + i, gb);
+        load8(xr + i, xb);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dot = acc_prod(dot, gb[j], xb[j]);
+      }
+      dot = group_sum<WAVE>(dot) / D;
+      const float r3dot = r * r * r * dot;
+      for (int i = lane * 8; i < D; i += WAVE * 8) {
+        load8(dyr + i, gb);
+        load8(xr + i, xb);
+        u16x8 out;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) out[j] = f2b(rmsnorm_bwd_elem(j, r, gb[j], xb[j], r3dot));
+        if (dsr) {
+          const u16x8 a = *(const u16x8*)(dsr + i);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) out[j] = f2b(b2f(a[j]) + b2f(out[j]));
+        }
+        *(u16x8*)(dxr + i) = out;
+      }
     }
   }
 }
@@ -135,7 +317,11 @@ __global__ void rmsnorm_bwd_bf16(const u16* __restrict__ dy, const u16* __restri
 // Vectorized: C/8 lanes per row, u16x8 loads (8 elems = 4 interleaved RoPE
 // pairs per lane, so the GPT-J rotation stays lane-local); a wave covers
 // 64/(C/8) rows; reductions via width-(C/8) shuffles.
+// NROLE = 3: q, k and the v transpose copy. NROLE = 2: q and k rows only
+// (B*T*H*2 rows); v is then read from the packed projection by the
+// attention kernels and never copied.
 // ============================================================
+template <int NROLE>
 __global__ void qkv_prep_fwd_kernel(const u16* __restrict__ qkv,
                                     const float* __restrict__ qw,
                                     const float* __restrict__ kw,
@@ -150,20 +336,20 @@ __global__ void qkv_prep_fwd_kernel(const u16* __restrict__ qkv,
   const int RPW = WAVE / LPR;            // rows per wave
   const int sub = lane_id() % LPR;       // lane's slot within its row
   const int rsub = lane_id() / LPR;      // which row of the wave
-  const unsigned nrows = (unsigned)(B * T * H * 3);
+  const unsigned nrows = (unsigned)(B * T * H * NROLE);
   const unsigned row0 = ((unsigned)blockIdx.x * (blockDim.x / WAVE) + wave_id()) * RPW + rsub;
   const unsigned rstep = (unsigned)gridDim.x * (blockDim.x / WAVE) * RPW;
   for (unsigned row = row0; row < nrows; row += rstep) {
     const unsigned h = row % (unsigned)H;
     const unsigned rest = row / (unsigned)H;
-    const unsigned role = rest % 3u;
-    const unsigned bt = rest / 3u;           // = b*T + t
+    const unsigned role = rest % (unsigned)NROLE;
+    const unsigned bt = rest / (unsigned)NROLE;  // = b*T + t
     const unsigned t = bt % (unsigned)T;
     const unsigned b = bt / (unsigned)T;
     const u16* src = qkv + (((long)bt * 3 + role) * H + h) * C + sub * 8;
     const long out_off = ((((long)b * H + h) * T + t) * C) + sub * 8;
     u16x8 raw = *(const u16x8*)src;
-    if (role == 2) {  // V: straight transpose copy
+    if (NROLE == 3 && role == 2) {  // V: straight transpose copy
       *(u16x8*)(v + out_off) = raw;
       continue;
     }
@@ -206,6 +392,12 @@ __global__ void qkv_prep_fwd_kernel(const u16* __restrict__ qkv,
 }
 
 // Backward: dq,dk,dv (B,H,T,C) -> dqkv (B,T,3,H,C); dqw,dkw via partials.
+// WITH_V = false: only slots 0 and 1 of dqkv are written (slot 2 belongs to
+// the attention backward, which writes dV there itself) and dv is not read.
+// The V rows stay in the row sequence and are skipped without a memory
+// access: every thread then sums the same q/k rows in the same order as with
+// WITH_V = true, so dqw and dkw are bit-identical between the two.
+template <bool WITH_V>
 __global__ void qkv_prep_bwd_kernel(const u16* __restrict__ dq,
                                     const u16* __restrict__ dk,
                                     const u16* __restrict__ dv,
@@ -237,11 +429,12 @@ __global__ void qkv_prep_bwd_kernel(const u16* __restrict__ dq,
     const unsigned rest = row / (unsigned)H;
     const unsigned role = rest % 3u;
     const unsigned bt = rest / 3u;           // = b*T + t
+    if (!WITH_V && role == 2) continue;
     const unsigned t = bt % (unsigned)T;
     const unsigned b = bt / (unsigned)T;
     u16* dst = dqkv + (((long)bt * 3 + role) * H + h) * C + sub * 8;
     const long in_off = ((((long)b * H + h) * T + t) * C) + sub * 8;
-    if (role == 2) {
+    if (WITH_V && role == 2) {
       *(u16x8*)dst = *(const u16x8*)(dv + in_off);
       continue;
     }

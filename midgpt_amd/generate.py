@@ -7,14 +7,24 @@ sequence fits in block_size (the reference re-runs the full forward per
 token). Once the window slides past block_size we fall back to the
 reference's recompute-from-cropped-window behavior so RoPE positions
 match exactly.
+
+Two decode paths. The native one (``KVCache`` + ``decode_step``) keeps K and V
+in one preallocated buffer and runs the step on the HIP decode kernels
+(``ops.kv_append`` / ``ops.decode_attention`` / ``ops.prefill_attention``);
+``generate`` takes it for a bf16 model on the GPU with head dim 64 or 128 and
+block_size % 128 == 0. Everything else (CPU, other dtypes and shapes, or
+``MIDGPT_DECODE_REF=1``, read at call time, for A/B) runs the eager path
+below, built from the fp32 reference ops.
 """
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 import torch.nn.functional as F
 
+from midgpt_amd import ops
 from midgpt_amd.ops import reference as ref
 
 
@@ -32,7 +42,7 @@ def _attn_cached(q, k, v):
     return torch.matmul(a, v)
 
 
-def _forward_cached(model, idx_new: torch.Tensor, cache: list, pos: int):
+def _eager_step(model, idx_new: torch.Tensor, cache: list, pos: int):
     """Run idx_new (B, Tnew) through the model appending to cache; returns
     last-position logits (B, V)."""
     cfg = model.config
@@ -65,6 +75,119 @@ def _forward_cached(model, idx_new: torch.Tensor, cache: list, pos: int):
     return model.lm_head(x)[:, -1]
 
 
+class KVCache:
+    """Preallocated K/V of every layer for ``batch_size`` sequences of up to
+    block_size positions: one buffer (n_layer, 2, B, H, block_size, C), with
+    per-layer views ``k[l]`` / ``v[l]`` of shape (B, H, block_size, C) and the
+    number of valid positions ``pos`` kept on the host. Rows >= pos hold
+    stale or uninitialised data and are never read."""
+
+    def __init__(self, model, batch_size: int, device=None, dtype=None):
+        cfg = model.config
+        device = model.wte.device if device is None else device
+        dtype = model.wte.dtype if dtype is None else dtype
+        self.block_size = cfg.block_size
+        self.buf = torch.empty(cfg.n_layer, 2, batch_size, cfg.n_head,
+                               cfg.block_size, cfg.head_dim, device=device,
+                               dtype=dtype)
+        self.k = [self.buf[li, 0] for li in range(cfg.n_layer)]
+        self.v = [self.buf[li, 1] for li in range(cfg.n_layer)]
+        # the kernels take fp32 LN weights: convert once, not per token
+        self.ln_w = [(blk.attn.q_ln_weight.detach().float(),
+                      blk.attn.k_ln_weight.detach().float())
+                     for blk in model.blocks]
+        self.pos = 0
+
+    def reset(self):
+        self.pos = 0
+
+
+def _attend_cached(qkv, qw, kw, sin, cos, k_cache, v_cache, pos):
+    """Append qkv (B,Tn,3,H,C) at pos and attend: -> o (B,Tn,H*C)."""
+    Tn = qkv.shape[1]
+    fits = not qkv.is_cuda or -(-Tn // 128) * 128 <= k_cache.shape[2]
+    if pos == 0 and Tn > 16 and fits:
+        return ops.prefill_attention(qkv, qw, kw, sin, cos, k_cache, v_cache)
+    outs = []
+    for s in range(0, Tn, 16):  # decode_attention takes at most 16 rows
+        chunk = qkv[:, s:s + 16]
+        q = ops.kv_append(chunk, qw, kw, sin, cos, k_cache, v_cache, pos + s)
+        outs.append(ops.decode_attention(q, k_cache, v_cache,
+                                         pos + s + chunk.shape[1]))
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+
+
+@torch.no_grad()
+def decode_step(model, idx_new: torch.Tensor, cache: KVCache) -> torch.Tensor:
+    """Run idx_new (B, Tn) at positions cache.pos .. cache.pos+Tn-1, appending
+    their K/V to the cache; returns the last position's logits (B, V)."""
+    cfg = model.config
+    H, C = cfg.n_head, cfg.head_dim
+    B, Tn = idx_new.shape
+    pos = cache.pos
+    if pos + Tn > cache.block_size:
+        raise RuntimeError(f"decode_step: positions [{pos}, {pos + Tn}) exceed "
+                           f"block_size {cache.block_size}")
+    sin, cos = model.rope_sin, model.rope_cos
+    x = F.embedding(idx_new, model.wte)
+    pending = None  # residual-pending form of GPT.forward
+    for li, blk in enumerate(model.blocks):
+        if pending is None:
+            h = ops.rmsnorm(x, None, 1e-6)
+        else:
+            x, h = ops.add_rmsnorm(x, pending, 1e-6)
+        qkv = blk.attn.c_attn(h).view(B, Tn, 3, H, C)
+        qw, kw = cache.ln_w[li]
+        o = _attend_cached(qkv, qw, kw, sin, cos, cache.k[li], cache.v[li], pos)
+        x, h = ops.add_rmsnorm(x, blk.attn.c_proj(o), 1e-6)
+        pending = blk.mlp(h)
+    cache.pos = pos + Tn
+    if pending is None:  # no blocks
+        h = ops.rmsnorm(x[:, -1:], None, 1e-5)
+    else:
+        _, h = ops.add_rmsnorm(x[:, -1:], pending[:, -1:], 1e-5)
+    return model.lm_head(h)[:, -1]
+
+
+def decode_ref() -> bool:
+    """MIDGPT_DECODE_REF=1 (read at call time) keeps ``generate`` on the
+    eager decode path: the A/B handle for the native one."""
+    return os.environ.get("MIDGPT_DECODE_REF") == "1"
+
+
+def native_decode(model) -> bool:
+    """Whether ``generate`` decodes this model on the HIP decode kernels."""
+    cfg = model.config
+    return (model.wte.is_cuda and model.wte.dtype == torch.bfloat16
+            and model.rope_sin.dtype == torch.float32
+            and cfg.head_dim in (64, 128) and cfg.block_size % 128 == 0
+            and not decode_ref())
+
+
+def decode_stepper(model, batch_size: int):
+    """step(tokens (B,Tn), pos) -> last-position logits (B,V) on the path
+    ``generate`` takes for this model: native (``KVCache`` + ``decode_step``)
+    or eager. pos is the absolute position of tokens[:, 0]; pos == 0 starts a
+    new sequence, otherwise it must continue the previous call."""
+    if native_decode(model):
+        kv = KVCache(model, batch_size)
+
+        def step(tokens, pos):
+            if pos == 0:
+                kv.reset()
+            assert pos == kv.pos, (pos, kv.pos)
+            return decode_step(model, tokens, kv)
+    else:
+        cache = [None] * model.config.n_layer
+
+        @torch.no_grad()
+        def step(tokens, pos):
+            if pos == 0:
+                cache[:] = [None] * model.config.n_layer
+            return _eager_step(model, tokens, cache, pos)
+    return step
+
+
 @torch.no_grad()
 def generate(model, idx: torch.Tensor, max_new_tokens: int,
              temperature: float = 1.0, top_k: int | None = None,
@@ -72,22 +195,19 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int,
     """idx (B, T0) int64 -> (B, T0 + max_new_tokens)."""
     model.eval()
     block = model.config.block_size
-    cache = [None] * model.config.n_layer
+    step = decode_stepper(model, idx.shape[0])
     # prompts longer than block_size condition on the last block_size tokens
     # (reference sample.py:74-81 crops to the trailing window)
-    logits = _forward_cached(model, idx[:, -block:], cache, 0)
+    logits = step(idx[:, -block:], 0)
     for _ in range(max_new_tokens):
         nxt = _sample(logits, temperature, top_k, generator)
         idx = torch.cat([idx, nxt[:, None]], dim=1)
         if idx.shape[1] <= block:
-            logits = _forward_cached(model, nxt[:, None], cache,
-                                     idx.shape[1] - 1)
+            logits = step(nxt[:, None], idx.shape[1] - 1)
         else:
-            # window slid: reference behavior — recompute cropped window
-            win = idx[:, -block:]
-            cache = [None] * model.config.n_layer
-            logits = _forward_cached(model, win, cache, 0)
-            cache = [None] * model.config.n_layer  # cache positions invalid
+            # window slid: reference behavior — recompute the cropped window
+            # from position 0 (the cached positions are invalid from here on)
+            logits = step(idx[:, -block:], 0)
     return idx
 
 

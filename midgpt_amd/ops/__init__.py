@@ -421,6 +421,115 @@ def qkv_attention(qkv, q_ln_weight, k_ln_weight, sin, cos,
 
 
 # ----------------------------------------------------------------------------
+# KV-cache decode (inference only, no autograd). Caches are (B,H,Tmax,C) and
+# are written in place. GPU: csrc/decode.hip; CPU or MIDGPT_FORCE_REF=1: the
+# same semantics in fp32 torch.
+# ----------------------------------------------------------------------------
+def _check_append(qkv, sin, cos, k_cache, v_cache, pos):
+    B, Tn, three, H, C = qkv.shape
+    if three != 3 or k_cache.shape != v_cache.shape or \
+            tuple(k_cache.shape[:2]) + (k_cache.shape[3],) != (B, H, C):
+        raise RuntimeError("kv_append: qkv must be (B,Tn,3,H,C) and the caches (B,H,Tmax,C)")
+    Tmax = k_cache.shape[2]
+    if Tn < 1 or pos < 0 or pos + Tn > Tmax:
+        raise RuntimeError(f"kv_append: rows [{pos}, {pos + Tn}) do not fit a "
+                           f"cache of {Tmax} rows")
+    if sin.shape[0] < pos + Tn or cos.shape[0] < pos + Tn:
+        raise RuntimeError(f"kv_append: sin/cos tables have {sin.shape[0]} rows, "
+                           f"position {pos + Tn - 1} needed")
+
+
+def kv_append(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
+              pos: int, eps: float = 1e-6):
+    """QK-LayerNorm + RoPE of Tn new tokens at absolute positions
+    pos .. pos+Tn-1. qkv (B,Tn,3,H,C); sin/cos are the FULL tables
+    (rows >= pos+Tn, C/2). Writes K and V rows [pos, pos+Tn) of the caches in
+    place (nothing else) and returns q (B,H,Tn,C)."""
+    pos = int(pos)
+    _check_append(qkv, sin, cos, k_cache, v_cache, pos)
+    if _use_hip(qkv):
+        return _C.kv_append(qkv.contiguous(), q_ln_weight, k_ln_weight, sin, cos,
+                            k_cache, v_cache, pos, eps)
+    Tn = qkv.shape[1]
+    s, c = sin[pos:pos + Tn], cos[pos:pos + Tn]
+    q = ref.qk_layernorm(qkv[:, :, 0].permute(0, 2, 1, 3), q_ln_weight, eps)
+    k = ref.qk_layernorm(qkv[:, :, 1].permute(0, 2, 1, 3), k_ln_weight, eps)
+    k_cache[:, :, pos:pos + Tn] = ref.apply_rope(k, s, c)
+    v_cache[:, :, pos:pos + Tn] = qkv[:, :, 2].permute(0, 2, 1, 3)
+    return ref.apply_rope(q, s, c).contiguous()
+
+
+def _decode_attention_ref(q, k_cache, v_cache, kv_len):
+    """End-aligned causal attention in fp32: row i of Tq sees keys
+    [0, kv_len - Tq + i]. -> (B,Tq,H*C) in q's dtype."""
+    B, H, Tq, C = q.shape
+    k = k_cache[:, :, :kv_len].float()
+    v = v_cache[:, :, :kv_len].float()
+    s = torch.matmul(q.float(), k.transpose(-1, -2)) / math.sqrt(C)
+    qpos = torch.arange(kv_len - Tq, kv_len, device=q.device)[:, None]
+    kpos = torch.arange(kv_len, device=q.device)[None, :]
+    s = s.masked_fill(kpos > qpos, float("-inf"))
+    o = torch.matmul(torch.softmax(s, dim=-1), v).to(q.dtype)
+    return o.transpose(1, 2).reshape(B, Tq, H * C)
+
+
+def decode_attention(q, k_cache, v_cache, kv_len: int, num_splits: int = 0):
+    """q (B,H,Tq,C), 1 <= Tq <= 16: the last Tq of the cache's first kv_len
+    positions. Causal, end-aligned, scale 1/sqrt(C), fp32 softmax. Returns o
+    (B,Tq,H*C). ``num_splits`` cuts the key range into that many slices over
+    the grid (0: chosen from the sizes and the CU count; <= 64)."""
+    kv_len, num_splits = int(kv_len), int(num_splits)
+    B, H, Tq, C = q.shape
+    if _use_hip(q):
+        return _C.attn_decode(q.contiguous(), k_cache, v_cache, kv_len,
+                              num_splits).view(B, Tq, H * C)
+    if kv_len > k_cache.shape[2]:
+        raise RuntimeError(f"decode_attention: kv_len {kv_len} exceeds the cache "
+                           f"({k_cache.shape[2]})")
+    if not 1 <= Tq <= min(16, kv_len):
+        raise RuntimeError("decode_attention: 1 <= Tq <= min(16, kv_len) required "
+                           f"(Tq {Tq}, kv_len {kv_len})")
+    if not 0 <= num_splits <= 64:
+        raise RuntimeError("decode_attention: num_splits must be in [0, 64]")
+    return _decode_attention_ref(q, k_cache, v_cache, kv_len)
+
+
+def prefill_attention(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
+                      eps: float = 1e-6):
+    """A whole prompt at position 0: qkv (B,Tn,3,H,C) -> o (B,Tn,H*C), with
+    K and V rows [0, Tn) of the caches written in place.
+
+    On GPU the prompt runs on the MFMA flash kernel, not row by row: qkv is
+    zero-padded along T to the next multiple of 128 (which must fit the
+    cache), qkv_prep_fwd and attn_fwd_packed run unchanged, and rows [0, Tn)
+    are kept. Padding rows are harmless: LN of a zero row is finite and
+    causality hides them from the real rows."""
+    B, Tn, _, H, C = qkv.shape
+    if not _use_hip(qkv):
+        q = kv_append(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache, 0, eps)
+        return _decode_attention_ref(q, k_cache, v_cache, Tn)
+    _check_append(qkv, sin, cos, k_cache, v_cache, 0)
+    Tp = -(-Tn // 128) * 128
+    if Tp > k_cache.shape[2]:
+        raise RuntimeError(f"prefill_attention: {Tn} rows pad to {Tp}, over the "
+                           f"cache's {k_cache.shape[2]}")
+    pad = Tp - Tn
+    if pad:
+        qkv = torch.nn.functional.pad(qkv, (0, 0, 0, 0, 0, 0, 0, pad))
+    sin, cos = sin[:Tp], cos[:Tp]
+    if sin.shape[0] < Tp:  # tables end inside the padding: any finite row does
+        extra = (0, 0, 0, Tp - sin.shape[0])
+        sin = torch.nn.functional.pad(sin, extra)
+        cos = torch.nn.functional.pad(cos, extra)
+    q, k, v, _, _ = _C.qkv_prep_fwd(qkv.contiguous(), q_ln_weight, k_ln_weight,
+                                    sin, cos, eps)
+    o, _ = _C.attn_fwd_packed(q, k, v)          # (B,Tp,H,C)
+    k_cache[:, :, :Tn].copy_(k[:, :, :Tn])
+    v_cache[:, :, :Tn].copy_(v[:, :, :Tn])
+    return o[:, :Tn].reshape(B, Tn, H * C)
+
+
+# ----------------------------------------------------------------------------
 # GELU (tanh approx) fwd/bwd (reference src/model.py:30; plan K7): a
 # hand-written u16x8 elementwise pair replacing the torch library kernels
 # (same numerics as F.gelu(approximate="tanh"); fp32 internal).

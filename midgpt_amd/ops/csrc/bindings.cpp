@@ -905,6 +905,135 @@ torch::Tensor gelu_bwd(torch::Tensor dy, torch::Tensor x) {
 }
 
 // ---------------------------------------------------------------------------
+// KV-cache decode (decode.hip). Caches are (B,H,Tmax,C) bf16, contiguous.
+static void check_decode_cache(const torch::Tensor& k_cache, const torch::Tensor& v_cache,
+                               int B, int H, int C, const char* who) {
+  CHECK_GPU(k_cache); CHECK_GPU(v_cache);
+  TORCH_CHECK(k_cache.scalar_type() == torch::kBFloat16 &&
+              v_cache.scalar_type() == torch::kBFloat16, who, ": caches must be bf16");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(0) == B && k_cache.size(1) == H &&
+              k_cache.size(3) == C && v_cache.sizes() == k_cache.sizes(),
+              who, ": caches must both be (B,H,Tmax,C)");
+  TORCH_CHECK(C == 64 || C == 128, who, ": head dim 64 or 128 (got ", C, ")");
+}
+
+// sin/cos are the FULL tables (rows >= pos+Tn, C/2) fp32; fp32 LN weights are
+// used in place, others converted.
+torch::Tensor kv_append(torch::Tensor qkv, torch::Tensor qw, torch::Tensor kw,
+                        torch::Tensor sin_t, torch::Tensor cos_t,
+                        torch::Tensor k_cache, torch::Tensor v_cache, int64_t pos,
+                        double eps) {
+  CHECK_GPU(qkv); CHECK_GPU(sin_t); CHECK_GPU(cos_t); CHECK_GPU(qw); CHECK_GPU(kw);
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "kv_append: qkv must be bf16");
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "kv_append: qkv must be (B,Tn,3,H,C)");
+  int B = qkv.size(0), Tn = qkv.size(1), H = qkv.size(3), C = qkv.size(4);
+  check_decode_cache(k_cache, v_cache, B, H, C, "kv_append");
+  const int64_t Tmax = k_cache.size(2);
+  TORCH_CHECK(Tn >= 1, "kv_append: no new tokens");
+  TORCH_CHECK(pos >= 0 && pos + Tn <= Tmax, "kv_append: rows [", pos, ", ", pos + Tn,
+              ") do not fit a cache of ", Tmax, " rows");
+  TORCH_CHECK(qw.numel() == C && kw.numel() == C, "kv_append: LN weights must be (C,)");
+  TORCH_CHECK(sin_t.scalar_type() == torch::kFloat && cos_t.scalar_type() == torch::kFloat &&
+              sin_t.dim() == 2 && sin_t.size(1) == C / 2 && cos_t.sizes() == sin_t.sizes(),
+              "kv_append: sin/cos must be fp32 (rows, C/2)");
+  TORCH_CHECK(sin_t.size(0) >= pos + Tn, "kv_append: sin/cos tables have ", sin_t.size(0),
+              " rows, position ", pos + Tn - 1, " needed");
+  auto q = torch::empty({B, H, Tn, C}, qkv.options());
+  auto qwf = qw.to(torch::kFloat);
+  auto kwf = kw.to(torch::kFloat);
+  const long nrows = (long)B * Tn * H * 3;
+  const int rpb = 4 * (WAVE / (C / 8));  // rows per 256-thread block
+  const long grid = std::min((nrows + rpb - 1) / rpb, (long)16384);
+  hipLaunchKernelGGL(kv_append_kernel, dim3(grid), dim3(256), 0, cur_stream(),
+                     (const u16*)qkv.data_ptr(), qwf.data_ptr<float>(),
+                     kwf.data_ptr<float>(), sin_t.data_ptr<float>(),
+                     cos_t.data_ptr<float>(), (u16*)q.data_ptr(),
+                     (u16*)k_cache.data_ptr(), (u16*)v_cache.data_ptr(),
+                     B, Tn, H, C, (long)Tmax, (long)pos, (float)eps);
+  launch_check();
+  return q;
+}
+
+static int decode_cu_count() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipGetDeviceProperties(&prop, dev) == hipSuccess)
+      cus = prop.multiProcessorCount;
+    if (cus <= 0) cus = 256;
+  }
+  return cus;
+}
+
+// num_splits = 0: as many slices as it takes to put DECODE_BLOCKS_PER_CU
+// block on every CU, but no slice shorter than DECODE_MIN_SLICE keys. Measured
+// (profiles/decode.md): one 256-thread block per CU already keeps ~32 KiB of
+// loads in flight there and more slices only add partials traffic; the
+// combine launch costs about as much as streaming 300 keys in one block, so
+// a range under 2 x 256 keys is not cut at all.
+constexpr int DECODE_BLOCKS_PER_CU = 1;
+constexpr int DECODE_MIN_SLICE = 256;
+constexpr int DECODE_MAX_SPLITS = 64;
+
+int64_t attn_decode_auto_splits(int64_t rows, int64_t kv_len, int64_t cus) {
+  const int64_t want = (DECODE_BLOCKS_PER_CU * cus + rows - 1) / rows;
+  const int64_t fit = kv_len / DECODE_MIN_SLICE;
+  return std::max<int64_t>(1, std::min<int64_t>({want, fit, DECODE_MAX_SPLITS}));
+}
+
+// q (B,H,Tq,C): the last Tq of kv_len positions; row i sees keys
+// [0, kv_len - Tq + i]. Returns o (B,Tq,H,C).
+torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+                          int64_t kv_len, int64_t num_splits) {
+  CHECK_GPU(q);
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn_decode: q must be bf16");
+  TORCH_CHECK(q.dim() == 4, "attn_decode: q must be (B,H,Tq,C)");
+  int B = q.size(0), H = q.size(1), Tq = q.size(2), C = q.size(3);
+  check_decode_cache(k_cache, v_cache, B, H, C, "attn_decode");
+  const int64_t Tmax = k_cache.size(2);
+  TORCH_CHECK(kv_len <= Tmax, "attn_decode: kv_len ", kv_len, " exceeds the cache (", Tmax, ")");
+  TORCH_CHECK(Tq >= 1 && Tq <= 16 && Tq <= kv_len,
+              "attn_decode: 1 <= Tq <= min(16, kv_len) required (Tq ", Tq, ", kv_len ",
+              kv_len, ")");
+  TORCH_CHECK(num_splits >= 0 && num_splits <= DECODE_MAX_SPLITS,
+              "attn_decode: num_splits must be in [0, ", DECODE_MAX_SPLITS, "]");
+  const long rows = (long)B * H * Tq;
+  TORCH_CHECK(rows > 0 && rows < (1L << 31) && kv_len < (1L << 31),
+              "attn_decode: size out of range");
+  if (num_splits == 0)
+    num_splits = attn_decode_auto_splits(rows, kv_len, decode_cu_count());
+  const int S = (int)num_splits;
+  auto o = torch::empty({B, Tq, H, C}, q.options());
+  torch::Tensor ws_acc, ws_ml;
+  float *accp = nullptr, *mlp = nullptr;
+  if (S > 1) {
+    ws_acc = torch::empty({rows, S, C}, q.options().dtype(torch::kFloat));
+    ws_ml = torch::empty({rows, S, 2}, q.options().dtype(torch::kFloat));
+    accp = ws_acc.data_ptr<float>();
+    mlp = ws_ml.data_ptr<float>();
+  }
+  const float scale = 1.0f / std::sqrt((float)C);
+#define LAUNCH_DECODE(CC)                                                         \
+  hipLaunchKernelGGL(attn_decode_kernel<CC>, dim3(rows, S), dim3(256), 0,         \
+                     cur_stream(), (const u16*)q.data_ptr(),                      \
+                     (const u16*)k_cache.data_ptr(), (const u16*)v_cache.data_ptr(), \
+                     (u16*)o.data_ptr(), accp, mlp, H, Tq, (long)Tmax, (int)kv_len, \
+                     S, scale)
+  if (C == 128) LAUNCH_DECODE(128);
+  else LAUNCH_DECODE(64);
+#undef LAUNCH_DECODE
+  launch_check();
+  if (S > 1) {
+    hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(rows), dim3(C), 0, cur_stream(),
+                       accp, mlp, (u16*)o.data_ptr(), H, Tq, C, S);
+    launch_check();
+  }
+  return o;
+}
+
+// ---------------------------------------------------------------------------
 torch::Tensor probe_mfma(torch::Tensor A, torch::Tensor B) {
   CHECK_GPU(A); CHECK_GPU(B);
   auto D = torch::zeros({32, 32}, A.options());
@@ -946,6 +1075,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"),
           py::arg("dqkv"), py::arg("p") = 0.0, py::arg("seed") = 0,
           py::arg("stage_do") = true);
+  mod.def("kv_append", &kv_append, py::arg("qkv"), py::arg("qw"), py::arg("kw"),
+          py::arg("sin"), py::arg("cos"), py::arg("k_cache"), py::arg("v_cache"),
+          py::arg("pos"), py::arg("eps") = 1e-6);
+  mod.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"),
+          py::arg("v_cache"), py::arg("kv_len"), py::arg("num_splits") = 0);
+  mod.def("attn_decode_auto_splits", &attn_decode_auto_splits, py::arg("rows"),
+          py::arg("kv_len"), py::arg("cus"));
   mod.def("embedding_bwd", &embedding_bwd);
   mod.def("gelu_fwd", &gelu_fwd);
   mod.def("gelu_bwd", &gelu_bwd);

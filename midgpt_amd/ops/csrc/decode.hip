@@ -1,0 +1,230 @@
+// KV-cache decode kernels for gfx950 (bf16, head dim C in {64, 128}).
+//
+//   kv_append_kernel     QK-LayerNorm + RoPE of Tn new tokens at absolute
+//                        position pos; q goes to (B,H,Tn,C), the K and V rows
+//                        straight into the (B,H,Tmax,C) caches.
+//   attn_decode_kernel   Tq <= 16 query rows against the cache, split-KV.
+//   attn_decode_combine_kernel   merges the per-slice partials.
+//
+// Decode attention is a memory-bound stream over K and V with one query row
+// per head: no MFMA, no LDS staging. K/V rows go straight to VGPRs with
+// 16-byte loads, C/8 lanes per key row.
+#pragma once
+#include "common.h"
+
+// Same row sequence as qkv_prep_fwd_kernel<3> (row = ((b*Tn + t)*3 + role)*H
+// + h) and the same row body (qk_ln_rope_row, norms.hip); only the position
+// (pos + t) and the destinations differ.
+__global__ void kv_append_kernel(const u16* __restrict__ qkv,
+                                 const float* __restrict__ qw,
+                                 const float* __restrict__ kw,
+                                 const float* __restrict__ sin_t,
+                                 const float* __restrict__ cos_t,
+                                 u16* __restrict__ q, u16* __restrict__ k_cache,
+                                 u16* __restrict__ v_cache,
+                                 int B, int Tn, int H, int C, long Tmax, long pos,
+                                 float eps) {
+  const int LPR = C / 8;                 // lanes per row (8 or 16)
+  const int RPW = WAVE / LPR;            // rows per wave
+  const int sub = lane_id() % LPR;
+  const int rsub = lane_id() / LPR;
+  const long nrows = (long)B * Tn * H * 3;
+  const long row0 = ((long)blockIdx.x * (blockDim.x / WAVE) + wave_id()) * RPW + rsub;
+  const long rstep = (long)gridDim.x * (blockDim.x / WAVE) * RPW;
+  for (long row = row0; row < nrows; row += rstep) {
+    const long h = row % H;
+    const long rest = row / H;
+    const int role = (int)(rest % 3);
+    const long bt = rest / 3;            // = b*Tn + t
+    const long t = bt % Tn;
+    const long b = bt / Tn;
+    const u16x8 raw = *(const u16x8*)(qkv + ((bt * 3 + role) * H + h) * C + sub * 8);
+    const long cache_off = ((b * H + h) * Tmax + pos + t) * C + sub * 8;
+    if (role == 2) {
+      *(u16x8*)(v_cache + cache_off) = raw;
+      continue;
+    }
+    float mu, invstd;
+    const u16x8 out = qk_ln_rope_row(raw, role == 0 ? qw : kw,
+                                     sin_t + (pos + t) * (C / 2) + sub * 4,
+                                     cos_t + (pos + t) * (C / 2) + sub * 4, C, LPR,
+                                     sub, eps, mu, invstd);
+    if (role == 0)
+      *(u16x8*)(q + ((b * H + h) * Tn + t) * C + sub * 8) = out;
+    else
+      *(u16x8*)(k_cache + cache_off) = out;
+  }
+}
+
+#define DECODE_NEG_INF (-__builtin_inff())
+
+// exp(m - m_ref) as the weight of a partial with running max m when merged
+// under m_ref >= m. A partial that saw no key has m = -inf (and l = acc = 0):
+// its weight is 0, not exp(-inf - -inf) = NaN.
+DEVINL float decode_weight(float m, float m_ref) {
+  return m == DECODE_NEG_INF ? 0.f : __expf(m - m_ref);
+}
+
+// One block = one query row (b, h, i) x one slice of its keys. Row i of Tq
+// sees keys [0, limit) with limit = kv_len - Tq + i + 1; the slice is
+// [k0, k1) = the split-th of num_splits equal parts of that range, possibly
+// empty. No cache row >= limit is ever loaded (the cache tail is
+// uninitialised memory).
+//
+// 256 threads form G = 256/(C/8) lane groups; group g takes keys k0+g,
+// k0+g+G, ... in batches of U keys whose K and V loads (2*U 16-byte loads per
+// lane) are all issued before the first use. Scores, online softmax and the
+// P.V accumulation are fp32; every lane of a group carries the group's (m, l)
+// and its own 8 columns of acc. Groups merge by shuffles, waves through LDS.
+// num_splits == 1: writes o (B,Tq,H,C) bf16. Otherwise writes the slice's
+// fp32 (m, l) to ws_ml[row][split][2] and acc to ws_acc[row][split][C].
+template <int C>
+__global__ __launch_bounds__(256) void attn_decode_kernel(
+    const u16* __restrict__ q, const u16* __restrict__ k_cache,
+    const u16* __restrict__ v_cache, u16* __restrict__ o,
+    float* __restrict__ ws_acc, float* __restrict__ ws_ml,
+    int H, int Tq, long Tmax, int kv_len, int num_splits, float scale) {
+  constexpr int LPR = C / 8;
+  constexpr int G = 256 / LPR;
+  constexpr int U = 4;
+  constexpr int NWAVE = 256 / WAVE;
+  const int row = blockIdx.x;            // (b*H + h)*Tq + i
+  const int split = blockIdx.y;
+  const int i = row % Tq;
+  const int bh = row / Tq;
+  const int limit = kv_len - Tq + i + 1;
+  const int per = (limit + num_splits - 1) / num_splits;
+  const int k0 = split * per;
+  const int k1 = min(limit, k0 + per);
+  const int sub = threadIdx.x % LPR;
+  const int g = threadIdx.x / LPR;
+  const u16* kb = k_cache + (long)bh * Tmax * C + sub * 8;
+  const u16* vb = v_cache + (long)bh * Tmax * C + sub * 8;
+
+  float qf[8];
+  {
+    const u16x8 qr = *(const u16x8*)(q + (long)row * C + sub * 8);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) qf[j] = b2f(qr[j]);
+  }
+  float m = DECODE_NEG_INF, l = 0.f;
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+
+  // The first key of a batch (kk) is always inside the slice, so every batch
+  // has a finite maximum.
+  for (int kk = k0 + g; kk < k1; kk += G * U) {
+    u16x8 kr[U], vr[U];
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int key = kk + u * G;
+      ok[u] = key < k1;
+      kr[u] = 0;
+      vr[u] = 0;
+      if (ok[u]) {
+        kr[u] = *(const u16x8*)(kb + (long)key * C);
+        vr[u] = *(const u16x8*)(vb + (long)key * C);
+      }
+    }
+    float s[U];
+    float mb = DECODE_NEG_INF;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      float d = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) d += qf[j] * b2f(kr[u][j]);
+      d = group_sum<LPR>(d) * scale;
+      s[u] = ok[u] ? d : DECODE_NEG_INF;
+      mb = fmaxf(mb, s[u]);
+    }
+    const float mn = fmaxf(m, mb);
+    const float corr = __expf(m - mn);   // m = -inf on the first batch: 0
+    l *= corr;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] *= corr;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const float p = __expf(s[u] - mn); // 0 for a key outside the slice
+      l += p;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += p * b2f(vr[u][j]);
+    }
+    m = mn;
+  }
+
+  // merge the lane groups of a wave
+#pragma unroll
+  for (int off = LPR; off < WAVE; off <<= 1) {
+    const float m2 = __shfl_xor(m, off);
+    const float l2 = __shfl_xor(l, off);
+    const float mn = fmaxf(m, m2);
+    const float f1 = decode_weight(m, mn), f2 = decode_weight(m2, mn);
+    l = l * f1 + l2 * f2;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = acc[j] * f1 + __shfl_xor(acc[j], off) * f2;
+    m = mn;
+  }
+
+  // merge the waves
+  __shared__ float sm_acc[NWAVE][C];
+  __shared__ float sm_ml[NWAVE][2];
+  if (lane_id() < LPR) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sm_acc[wave_id()][sub * 8 + j] = acc[j];
+    if (lane_id() == 0) {
+      sm_ml[wave_id()][0] = m;
+      sm_ml[wave_id()][1] = l;
+    }
+  }
+  __syncthreads();
+  const int c = threadIdx.x;
+  if (c < C) {
+    float M = sm_ml[0][0];
+#pragma unroll
+    for (int w = 1; w < NWAVE; ++w) M = fmaxf(M, sm_ml[w][0]);
+    float L = 0.f, A = 0.f;
+#pragma unroll
+    for (int w = 0; w < NWAVE; ++w) {
+      const float f = decode_weight(sm_ml[w][0], M);
+      L += sm_ml[w][1] * f;
+      A += sm_acc[w][c] * f;
+    }
+    if (num_splits == 1) {
+      // split 0 of 1 holds key 0 at least: L > 0
+      const int b = bh / H, h = bh % H;
+      o[(((long)b * Tq + i) * H + h) * C + c] = f2b(A / L);
+    } else {
+      const long part = (long)row * num_splits + split;
+      ws_acc[part * C + c] = A;          // empty slice: M = -inf, L = A = 0
+      if (c == 0) {
+        ws_ml[part * 2] = M;
+        ws_ml[part * 2 + 1] = L;
+      }
+    }
+  }
+}
+
+// One block of C threads per query row: o = sum_s acc_s w_s / sum_s l_s w_s
+// with w_s = exp(m_s - max m). Slice 0 is never empty, so the sum of l is > 0.
+__global__ void attn_decode_combine_kernel(const float* __restrict__ ws_acc,
+                                           const float* __restrict__ ws_ml,
+                                           u16* __restrict__ o, int H, int Tq,
+                                           int C, int num_splits) {
+  const int row = blockIdx.x;
+  const int c = threadIdx.x;
+  const float* ml = ws_ml + (long)row * num_splits * 2;
+  const float* ac = ws_acc + (long)row * num_splits * C + c;
+  float M = DECODE_NEG_INF;
+  for (int s = 0; s < num_splits; ++s) M = fmaxf(M, ml[2 * s]);
+  float L = 0.f, A = 0.f;
+  for (int s = 0; s < num_splits; ++s) {
+    const float f = decode_weight(ml[2 * s], M);
+    L += ml[2 * s + 1] * f;
+    A += ac[(long)s * C] * f;
+  }
+  const int i = row % Tq, bh = row / Tq;
+  const int b = bh / H, h = bh % H;
+  o[(((long)b * Tq + i) * H + h) * C + c] = f2b(A / L);
+}

@@ -5,6 +5,7 @@
 #include "ce.hip"
 #include "adamw.hip"
 #include "attention.hip"
+#include "decode.hip"
 #include "embedding.hip"
 #include "gelu.hip"
 #include "probe.hip"

@@ -321,6 +321,45 @@ __global__ void add_rmsnorm_bwd_bf16(const u16* __restrict__ ds, const u16* __re
 // (B*T*H*2 rows); v is then read from the packed projection by the
 // attention kernels and never copied.
 // ============================================================
+// One Q or K row of the fused prep: LayerNorm over the head dim (weight, no
+// bias) then GPT-J RoPE, for the lane holding elements sub*8 .. sub*8+7 of the
+// row. srow/crow point at this lane's 4 sin/cos pairs of the row's position.
+// Shared by qkv_prep_fwd_kernel and kv_append_kernel (decode.hip): one body,
+// so a row appended to the KV cache has the bits the training kernel gives.
+DEVINL u16x8 qk_ln_rope_row(const u16x8 raw, const float* __restrict__ w,
+                            const float* __restrict__ srow,
+                            const float* __restrict__ crow, int C, int LPR,
+                            int sub, float eps, float& mu_out, float& invstd_out) {
+  float x[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = b2f(raw[j]);
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s += x[j];
+  // width-LPR reduction within the row's lane group
+  for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, LPR);
+  const float mu = s / C;
+  float ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { x[j] -= mu; ss += x[j] * x[j]; }
+  for (int o = LPR / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, LPR);
+  const float invstd = rsqrtf(ss / C + eps);
+  mu_out = mu;
+  invstd_out = invstd;
+  // normalize + weight + RoPE (pairs p = 4*sub + 0..3)
+  f32x4 sn = *(const f32x4*)srow;
+  f32x4 cs = *(const f32x4*)crow;
+  u16x8 out;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    float n0 = x[2 * p] * invstd * w[sub * 8 + 2 * p];
+    float n1 = x[2 * p + 1] * invstd * w[sub * 8 + 2 * p + 1];
+    out[2 * p] = f2b(n0 * cs[p] - n1 * sn[p]);
+    out[2 * p + 1] = f2b(n1 * cs[p] + n0 * sn[p]);
+  }
+  return out;
+}
+
 template <int NROLE>
 __global__ void qkv_prep_fwd_kernel(const u16* __restrict__ qkv,
                                     const float* __restrict__ qw,
@@ -356,36 +395,13 @@ __global__ void qkv_prep_fwd_kernel(const u16* __restrict__ qkv,
     const float* w = role == 0 ? qw : kw;
     u16* dst = role == 0 ? q : k;
     float* stats = role == 0 ? qstats : kstats;
-    float x[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = b2f(raw[j]);
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += x[j];
-    // width-LPR reduction within the row's lane group
-    for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, LPR);
-    const float mu = s / C;
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { x[j] -= mu; ss += x[j] * x[j]; }
-    for (int o = LPR / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, LPR);
-    const float invstd = rsqrtf(ss / C + eps);
+    float mu, invstd;
+    const u16x8 out = qk_ln_rope_row(raw, w, sin_t + t * (C / 2) + sub * 4,
+                                     cos_t + t * (C / 2) + sub * 4, C, LPR, sub,
+                                     eps, mu, invstd);
     if (sub == 0) {
       stats[2 * (((long)b * H + h) * T + t)] = mu;
       stats[2 * (((long)b * H + h) * T + t) + 1] = invstd;
-    }
-    // normalize + weight + RoPE (pairs p = 4*sub + 0..3)
-    const float* srow = sin_t + t * (C / 2) + sub * 4;
-    const float* crow = cos_t + t * (C / 2) + sub * 4;
-    f32x4 sn = *(const f32x4*)srow;
-    f32x4 cs = *(const f32x4*)crow;
-    u16x8 out;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      float n0 = x[2 * p] * invstd * w[sub * 8 + 2 * p];
-      float n1 = x[2 * p + 1] * invstd * w[sub * 8 + 2 * p + 1];
-      out[2 * p] = f2b(n0 * cs[p] - n1 * sn[p]);
-      out[2 * p + 1] = f2b(n1 * cs[p] + n0 * sn[p]);
     }
     *(u16x8*)(dst + out_off) = out;
   }

@@ -1,0 +1,174 @@
+"""Decode benchmarks (run on the GPU box; fails without a GPU).
+
+  --which kernels   attn_decode (+ combine) and kv_append microbench: time and
+                    achieved bytes/s against the HBM peak. The byte count is
+                    the algorithmic one, K and V read once:
+                    2 * B*H*kv_len*C * 2 bytes. Each call reads a different
+                    cache out of a ring of >= 1 GiB, so the 256 MiB Infinity
+                    Cache cannot hold the working set (in a real decode step
+                    the other layers' caches evict it in the same way).
+  --sweep           with kernels: every num_splits in 1,2,4,..,64 next to the
+                    automatic choice (the measurements behind the split rule).
+  --which e2e       generate() on the openwebtext_xl architecture, random
+                    weights, 128-token prompt + 256 new tokens, greedy: native
+                    path and MIDGPT_DECODE_REF=1 alternating in this process,
+                    each warmed up, host clock around a final synchronise.
+  --which count     one generate() of --new tokens on the path the
+                    environment selects and nothing else: run it under
+                    ``rocprofv3 --kernel-trace --stats`` at two values of
+                    --new; the difference in dispatches is launches per token.
+"""
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import argparse
+import statistics
+import time
+
+import torch
+
+from midgpt_amd import ops
+from midgpt_amd.ops import reference as ref
+
+assert torch.cuda.is_available(), "bench_decode.py needs a GPU"
+assert ops.have_ext(), f"HIP extension missing: {ops._C_ERR}"
+DEV = "cuda:0"
+BF = torch.bfloat16
+HBM_PEAK = 8.0e12       # bytes/s, MI355X HBM3E spec
+HBM_COPY = 6.29e12      # bytes/s, measured float4 copy
+RING_BYTES = 1 << 30
+
+
+def time_ring(fns, iters, warmup=10):
+    """Mean seconds per call, cycling through fns (one per ring slot)."""
+    n = len(fns)
+    for i in range(max(warmup, n)):
+        fns[i % n]()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(iters):
+        fns[i % n]()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters
+
+
+def bench_attn_decode(B, H, C, kv_len, sweep):
+    nbytes = 2 * B * H * kv_len * C * 2          # K and V once, bf16
+    ring = max(1, min(32, -(-RING_BYTES // nbytes)))
+    caches = [(torch.randn(B, H, kv_len, C, device=DEV, dtype=BF),
+               torch.randn(B, H, kv_len, C, device=DEV, dtype=BF))
+              for _ in range(ring)]
+    q = torch.randn(B, H, 1, C, device=DEV, dtype=BF)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    auto = ops._C.attn_decode_auto_splits(B * H, kv_len, cus)
+    iters = 200 if nbytes < (64 << 20) else 50
+    splits = [0] + ([s for s in (1, 2, 4, 8, 16, 32, 64)] if sweep else [])
+    for s in splits:
+        fns = [(lambda k=k, v=v: ops._C.attn_decode(q, k, v, kv_len, s))
+               for k, v in caches]
+        reps = [time_ring(fns, iters) for _ in range(3)]
+        t = statistics.median(reps)
+        tag = f"auto={auto}" if s == 0 else f"{s:4d}"
+        print(f"attn_decode B{B} H{H} C{C} kv{kv_len} splits {tag:>7}: "
+              f"{t*1e6:9.1f} us (min {min(reps)*1e6:.1f} max {max(reps)*1e6:.1f})  "
+              f"{nbytes/1e6:8.1f} MB  {nbytes/t/1e12:5.2f} TB/s  "
+              f"{100*nbytes/t/HBM_PEAK:5.1f}% of 8.0 TB/s peak, "
+              f"{100*nbytes/t/HBM_COPY:5.1f}% of 6.29 TB/s copy", flush=True)
+    del caches
+
+
+def bench_kv_append(B, H=16, C=128, Tmax=1024):
+    qkv = torch.randn(B, 1, 3, H, C, device=DEV, dtype=BF)
+    qw = torch.ones(C, device=DEV)
+    kw = torch.ones(C, device=DEV)
+    sin, cos = (t.contiguous() for t in ref.rope_tables(C, Tmax, device=DEV))
+    kc = torch.zeros(B, H, Tmax, C, device=DEV, dtype=BF)
+    vc = torch.zeros_like(kc)
+    fn = lambda: ops._C.kv_append(qkv, qw, kw, sin, cos, kc, vc, 500, 1e-6)
+    reps = [time_ring([fn], 500) for _ in range(3)]
+    nbytes = 2 * qkv.numel() * 2
+    print(f"kv_append   B{B} H{H} C{C} Tn1: {statistics.median(reps)*1e6:9.1f} us "
+          f"(min {min(reps)*1e6:.1f} max {max(reps)*1e6:.1f})  {nbytes/1e3:.1f} kB "
+          f"moved: launch-bound, back-to-back enqueue time", flush=True)
+
+
+def xl_model():
+    from midgpt_amd.config import load_config
+    from midgpt_amd.models.gpt import GPT
+    cfg = load_config("openwebtext_xl").model_config
+    torch.manual_seed(0)
+    with torch.device(DEV):
+        model = GPT(cfg)
+    model = model.to(BF).eval()
+    model.rope_sin = model.rope_sin.float()
+    model.rope_cos = model.rope_cos.float()
+    return model, cfg
+
+
+def timed_generate(model, idx, n_new, eager):
+    from midgpt_amd.generate import generate
+    if eager:
+        os.environ["MIDGPT_DECODE_REF"] = "1"
+    else:
+        os.environ.pop("MIDGPT_DECODE_REF", None)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = generate(model, idx, n_new, temperature=0.0)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    os.environ.pop("MIDGPT_DECODE_REF", None)
+    assert out.shape == (idx.shape[0], idx.shape[1] + n_new)
+    return dt
+
+
+def bench_e2e(reps, n_prompt=128, n_new=256):
+    model, cfg = xl_model()
+    print(f"e2e generate: openwebtext_xl ({cfg.n_layer} layers, {cfg.n_head} heads, "
+          f"head dim {cfg.head_dim}), prompt {n_prompt}, {n_new} new tokens, greedy; "
+          "time includes the prompt", flush=True)
+    for B in (1, 8):
+        idx = torch.randint(0, cfg.vocab_size, (B, n_prompt), device=DEV)
+        for eager in (False, True):                       # warm up both paths
+            timed_generate(model, idx, 16, eager)
+        res = {False: [], True: []}
+        for _ in range(reps):
+            for eager in (False, True):                   # alternating
+                res[eager].append(timed_generate(model, idx, n_new, eager))
+        for eager, name in ((False, "native"), (True, "eager (MIDGPT_DECODE_REF=1)")):
+            tps = sorted(B * n_new / t for t in res[eager])
+            print(f"e2e B{B} {name:28s}: tokens/s median {statistics.median(tps):8.1f} "
+                  f"min {tps[0]:8.1f} max {tps[-1]:8.1f}  "
+                  f"({statistics.median(res[eager])*1e3/n_new:6.2f} ms/step) over {reps} runs",
+                  flush=True)
+        med = {e: statistics.median(res[e]) for e in res}
+        print(f"e2e B{B} native/eager speed ratio (median): {med[True]/med[False]:.2f}x",
+              flush=True)
+
+
+def run_count(n_new):
+    model, cfg = xl_model()
+    idx = torch.randint(0, cfg.vocab_size, (1, 128), device=DEV)
+    from midgpt_amd.generate import generate, native_decode
+    print(f"count: native={native_decode(model)} new={n_new}", flush=True)
+    generate(model, idx, n_new, temperature=0.0)
+    torch.cuda.synchronize()
+
+
+if __name__ == "__main__":
+    p = argparse.ArgumentParser()
+    p.add_argument("--which", default="all", choices=["all", "kernels", "e2e", "count"])
+    p.add_argument("--sweep", action="store_true")
+    p.add_argument("--reps", type=int, default=3)
+    p.add_argument("--new", type=int, default=32)
+    args = p.parse_args()
+    if args.which in ("all", "kernels"):
+        for B in (1, 8, 64):
+            for kv in (128, 1024):
+                bench_attn_decode(B, 16, 128, kv, args.sweep)
+        for B in (1, 8, 64):
+            bench_attn_decode(B, 32, 128, 4096, args.sweep)   # 7B shape
+        for B in (1, 8, 64):
+            bench_kv_append(B)
+    if args.which in ("all", "e2e"):
+        bench_e2e(max(3, args.reps))
+    if args.which == "count":
+        run_count(args.new)

@@ -283,34 +283,23 @@ class _Attention(torch.autograd.Function):
                                                  dropout_p, ctx.seed)
             else:
                 dq, dk, dv = _C.attn_bwd(do.contiguous(), q, k, v, o, lse)
-        elif dropout_p > 0.0:
-            B, H, T, C = q.shape
-            scale = 1.0 / math.sqrt(C)
-            s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
-            mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
-            s = s.masked_fill(~mask, float("-inf"))
-            p = torch.exp(s - lse[..., None])          # undropped P, fp32
-            z = _cpu_dropout_scale(ctx.seed, B, H, T, dropout_p, p)
-            dof = do.float()
-            dv = torch.matmul((p * z).transpose(-1, -2), dof)
-            dp = torch.matmul(dof, v.float().transpose(-1, -2)) * z
-            # rowsum(dO*O) = sum_j P_ij dP_ij also holds for the dropped O
-            delta = (dof * o.float()).sum(dim=-1, keepdim=True)
-            ds = p * (dp - delta)
-            dq = torch.matmul(ds, k.float()) * scale
-            dk = torch.matmul(ds.transpose(-1, -2), q.float()) * scale
-            dq, dk, dv = dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
         else:
             B, H, T, C = q.shape
             scale = 1.0 / math.sqrt(C)
             s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
             mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
             s = s.masked_fill(~mask, float("-inf"))
-            p = torch.exp(s - lse[..., None])          # (B,H,T,T) fp32
+            p = torch.exp(s - lse[..., None])          # undropped P (B,H,T,T) fp32
             dof = do.float()
-            dv = torch.matmul(p.transpose(-1, -2), dof)
             dp = torch.matmul(dof, v.float().transpose(-1, -2))
-            delta = (dof * o.float()).sum(dim=-1, keepdim=True)  # rowsum(dO*O)
+            if dropout_p > 0.0:
+                z = _cpu_dropout_scale(ctx.seed, B, H, T, dropout_p, p)
+                dv = torch.matmul((p * z).transpose(-1, -2), dof)
+                dp = dp * z
+            else:
+                dv = torch.matmul(p.transpose(-1, -2), dof)
+            # rowsum(dO*O) = sum_j P_ij dP_ij also holds for the dropped O
+            delta = (dof * o.float()).sum(dim=-1, keepdim=True)
             ds = p * (dp - delta)
             dq = torch.matmul(ds, k.float()) * scale
             dk = torch.matmul(ds.transpose(-1, -2), q.float()) * scale

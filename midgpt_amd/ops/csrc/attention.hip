@@ -196,8 +196,8 @@ DEVINL bf16x8_t dlayout_to_afrag_keep(const float* s /*8 vals*/, uint32_t m8) {
 // DROP: attention dropout (philox.h). m, lsum and the saved LSE come from
 // the UNDROPPED P; only the P fragments fed to the PV MFMA are masked, and
 // 1/(1-p) is folded into the epilogue's 1/lsum.
-template <int C, int NW, int SPW, int MINW, bool DROP = false>
-__global__ __launch_bounds__(NW * 64, MINW) void attn_fwd_kernel(const u16* __restrict__ q,
+template <int C, int NW, int SPW, bool DROP = false>
+__global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const u16* __restrict__ q,
                                 const u16* __restrict__ k,
                                 const u16* __restrict__ v,
                                 u16* __restrict__ o, float* __restrict__ lse,
@@ -395,175 +395,13 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_fwd_kernel(const u16* __re
 }
 
 // ===========================================================================
-// Forward, DEPTH-2 prefetch variant (SPW=1): four LDS buffers, loads for
-// tile kt+2 issued while tile kt computes — each load gets ~2 compute
-// phases + a barrier to land instead of T14's single phase (the kernels
-// are SQ_WAIT memory-bound at 2 waves/SIMD; this deepens the cover at
-// +~12 VGPR). 4-tile unrolled loop keeps every stage object and buffer
-// index static (rule 20: runtime-indexed vector arrays go to scratch).
-// ===========================================================================
-template <int C, int NW>
-__global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d2_kernel(
-    const u16* __restrict__ q, const u16* __restrict__ k,
-    const u16* __restrict__ v, u16* __restrict__ o, float* __restrict__ lse,
-    int B, int H, int T, AttnStrides sv, AttnStrides so) {
-  constexpr int NCB = C / 32;
-  constexpr int NCH = C / 16;
-  const float scale = rsqrtf((float)C);
-  const long bh = blockIdx.x % ((long)B * H);
-  const int qb = blockIdx.x / (B * H);
-  const int q0 = qb * (NW * 32);
-  const int lane = lane_id();
-  const int w = wave_id();
-  const int qw0 = q0 + 32 * w;
-  const int myq = qw0 + (lane & 31);
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  u16* ldsK = (u16*)smem;                       // [4][32*C]
-  u16* ldsVt = (u16*)(smem + 4 * 32 * C * 2);   // [4][C*32]
-  float* obuf = (float*)smem;                   // epilogue reuse
-
-  const u16* qg = q + (bh * T) * C;
-  const u16* kg = k + (bh * T) * C;
-  const u16* vg = v + bh_base(sv, bh, H);
-
-  bf16x8_t qf[NCH];
-  {
-    const u16* qrow = qg + (long)myq * C;
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch)
-      qf[ch] = *(const bf16x8_t*)(qrow + 16 * ch + 8 * (lane >> 5));
-  }
-  f32x16 oacc[NCB];
-#pragma unroll
-  for (int cb = 0; cb < NCB; ++cb) oacc[cb] = (f32x16)(0.f);
-  float m = -1e30f, lsum = 0.f;
-
-  const int nkt = (q0 + NW * 32) / 32;  // multiple of NW (>= 8): % 4 == 0
-
-  auto tile_compute = [&](int kt, const u16* kb, const u16* vb) {
-    const int k0 = kt * 32;
-    if (k0 > qw0 + 31) return;  // wave-uniform
-    f32x16 s = (f32x16)(0.f);
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      bf16x8_t a = read_rm_frag<C>(kb, lane & 31, 16 * ch * 2 + 16 * (lane >> 5));
-      s = mfma_32x32x16_bf16(a, qf[ch], s);
-    }
-    float sv[16];
-    float mt = -1e30f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      sv[r] = (k0 + mfma_d_row(lane, r) > myq) ? -1e30f : s[r];
-      mt = fmaxf(mt, sv[r]);
-    }
-    mt = fmaxf(mt, __shfl_xor(mt, 32));
-    const float mn = fmaxf(m, mt);
-    const float alpha = __expf((m - mn) * scale);
-    const bool need_rescale = !__all(mt <= m);
-    m = mn;
-    float pp[16], psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      pp[r] = __expf((sv[r] - mn) * scale);
-      psum += pp[r];
-    }
-    psum += __shfl_xor(psum, 32);
-    lsum = lsum * alpha + psum;
-    if (need_rescale) {
-      float arow[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) arow[r] = shfl32(alpha, mfma_d_row(lane, r));
-#pragma unroll
-      for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[cb][r] *= arow[r];
-    }
-    bf16x8_t pf0 = dlayout_to_afrag(pp);
-    bf16x8_t pf1 = dlayout_to_afrag(pp + 8);
-#pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) {
-      bf16x8_t b0 = read_tr_frag(vb, 32 * cb + (lane & 31), 16 * (lane >> 5));
-      bf16x8_t b1 = read_tr_frag(vb, 32 * cb + (lane & 31), 32 + 16 * (lane >> 5));
-      oacc[cb] = mfma_32x32x16_bf16(pf0, b0, oacc[cb]);
-      oacc[cb] = mfma_32x32x16_bf16(pf1, b1, oacc[cb]);
-    }
-  };
-
-  // prologue: tile 0 staged synchronously; tile 1's loads issued (stO)
-  stage_rm<C, NW * 64>(kg, ldsK);
-  stage_tr<C, NW * 64>(vg, ldsVt, sv.r);
-  RmStage<C, NW * 64> kE, kO;
-  TrStage<C, NW * 64> vE, vO;
-  if (1 < nkt) { kO.load(kg + (long)32 * C); vO.load(vg + (long)32 * sv.r, sv.r); }
-  __syncthreads();
-
-#define FWD_D2_STEP(J, ST_LD, ST_WR, LBUF, WBUF)                              \
-  do {                                                                        \
-    if (kt + (J) + 2 < nkt) {                                                 \
-      k##ST_LD.load(kg + (long)(kt + (J) + 2) * 32 * C);                      \
-      v##ST_LD.load(vg + (long)(kt + (J) + 2) * 32 * sv.r, sv.r);             \
-    }                                                                         \
-    tile_compute(kt + (J), ldsK + (LBUF) * 32 * C, ldsVt + (LBUF) * C * 32);  \
-    if (kt + (J) + 1 < nkt) {                                                 \
-      k##ST_WR.write(ldsK + (WBUF) * 32 * C);                                 \
-      v##ST_WR.write_tr(ldsVt + (WBUF) * C * 32);                             \
-    }                                                                         \
-    __syncthreads();                                                          \
-  } while (0)
-
-  for (int kt = 0; kt < nkt; kt += 4) {
-    // invariant at loop top: buf0 = tile kt (ready); stO holds tile kt+1
-    FWD_D2_STEP(0, E, O, 0, 1);  // issue kt+2 (E); compute kt; write kt+1
-    FWD_D2_STEP(1, O, E, 1, 2);  // issue kt+3 (O); compute kt+1; write kt+2
-    FWD_D2_STEP(2, E, O, 2, 3);
-    FWD_D2_STEP(3, O, E, 3, 0);  // write kt+4 into buf0: invariant holds
-  }
-#undef FWD_D2_STEP
-
-  // epilogue: normalize, bounce through LDS, wide stores
-  const float rec = 1.f / lsum;
-  float rrow[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) rrow[r] = shfl32(rec, mfma_d_row(lane, r));
-  if (lane < 32) lse[bh * T + myq] = m * scale + __logf(lsum);
-  float* ob = obuf + w * 32 * 32;
-  u16* og = o + bh_base(so, bh, H) + (long)qw0 * so.r;
-#pragma unroll
-  for (int cb = 0; cb < NCB; ++cb) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = mfma_d_row(lane, r);
-      *(float*)((char*)ob + row * 128 + (((lane & 31) * 4) ^ ((row & 7) << 4))) =
-          oacc[cb][r] * rrow[r];
-    }
-    __builtin_amdgcn_s_waitcnt(0);
-    const int row = lane & 31;
-    const int c16 = 16 * (lane >> 5);
-    float tmp[16];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f32x4 t = *(const f32x4*)((char*)ob + row * 128 + (((c16 + 4 * i) * 4) ^ ((row & 7) << 4)));
-      tmp[4 * i] = t[0]; tmp[4 * i + 1] = t[1]; tmp[4 * i + 2] = t[2]; tmp[4 * i + 3] = t[3];
-    }
-    u16x8 out0, out1;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { out0[j] = f2b(tmp[j]); out1[j] = f2b(tmp[8 + j]); }
-    *(u16x8*)(og + (long)row * so.r + 32 * cb + c16) = out0;
-    *(u16x8*)(og + (long)row * so.r + 32 * cb + c16 + 8) = out1;
-    __builtin_amdgcn_s_waitcnt(0);
-  }
-}
-
-// ===========================================================================
 // Forward, PAIRED variant: two 32-row KV tiles per barrier round with ONE
 // merged online-softmax rescale — halves barrier rounds and O-rescale
 // passes vs the single-tile loop. nkt is always even (multiple of NW).
+// Launched for C=128 at NW=8 only (+4% there, -4% at C=64).
 // ===========================================================================
-// C=64 fits 3 waves/SIMD (168 VGPRs): ask for it rather than leave it to
-// the allocator's choice under a 2-wave bound.
 template <int C, int NW>
-__global__ __launch_bounds__(NW * 64, C == 64 ? 3 : 2) void attn_fwd2_kernel(
+__global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, u16* __restrict__ o, float* __restrict__ lse,
     int B, int H, int T, AttnStrides sv, AttnStrides so) {
@@ -798,8 +636,8 @@ __global__ void attn_delta_kernel(const u16* __restrict__ dO,
 // dS = P o (dP - delta) * scale. Registers 4g..4g+3 are four consecutive q
 // (4-aligned) at this lane's k: one Philox call per register group. The
 // 1/(1-p) of dV is applied once, in the epilogue.
-template <int C, int NW, int ABLATE = 0, int MINW = 2, bool DROP = false>
-__global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
+template <int C, int NW, bool DROP = false>
+__global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
     const u16* __restrict__ dO, const u16* __restrict__ q,
     const u16* __restrict__ k, const u16* __restrict__ v,
     const float* __restrict__ lse, const float* __restrict__ delta,
@@ -833,11 +671,11 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
   // K row fragments resident in registers (the L2 re-read variant was
   // measured -20% on dkv C=128 in a full-step profile despite removing
   // the 2-VGPR spill — the per-tile global loads add latency the spill
-  // never cost); re-read only under the MINW=3 squeeze experiment.
+  // never cost).
   // Under DROP at C=128 the keep mask and its select/scale code do not
   // fit beside 32 VGPRs of resident K (the DROP=false kernel already sits
   // at the 256 cap with 2 spills), so that variant re-reads K too.
-  constexpr bool KF_RES = (MINW <= 2) && !(DROP && C == 128);
+  constexpr bool KF_RES = !(DROP && C == 128);
   bf16x8_t kf[KF_RES ? NCH : 1];
   if (KF_RES) {
 #pragma unroll
@@ -872,7 +710,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
   for (int qt = qt0; qt < nqt; ++qt) {
     const int buf = (qt - qt0) & 1;
     const bool pre = qt + 1 < nqt;
-    if (ABLATE != 2 && pre) {  // T14 split: loads early
+    if (pre) {  // T14 split: loads early
       const long nb = (long)(qt + 1) * 32;
       qst.load(qg + nb * C);
       dost.load(dog + nb * sdo.r, sdo.r);
@@ -882,7 +720,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
       }
     }
     const int qbase = qt * 32;
-    if (ABLATE != 1 && qbase + 31 >= kw0) {  // not fully masked for this wave
+    if (qbase + 31 >= kw0) {  // not fully masked for this wave
       const u16* ldsQ = base + buf * TILE;
       const u16* ldsQt = ldsQ + 32 * C;
       const u16* ldsDO = ldsQt + C * 32;
@@ -914,32 +752,22 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int qrow = qbase + mfma_d_row(lane, r);
-        if (ABLATE == 3)
-          p[r] = s[r] * scale - lseb[mfma_d_row(lane, r)];  // no exp/mask
-        else
-          p[r] = (myk > qrow) ? 0.f
-               : __expf(s[r] * scale - lseb[mfma_d_row(lane, r)]);
+        p[r] = (myk > qrow) ? 0.f
+             : __expf(s[r] * scale - lseb[mfma_d_row(lane, r)]);
       }
       // dV += P^T x dO
       bf16x8_t pf0, pf1;
       if constexpr (DROP) {
         pf0 = dlayout_to_afrag_keep(p, keep);
         pf1 = dlayout_to_afrag_keep(p + 8, keep >> 8);
-      } else if (ABLATE == 4) {  // skip the permlane pack, keep p live
-        asm volatile("" :: "v"(p[0]), "v"(p[8]));
-        pf0 = kf[0]; pf1 = kf[0];
       } else {
         pf0 = dlayout_to_afrag(p);
         pf1 = dlayout_to_afrag(p + 8);
       }
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
-        bf16x8_t b0, b1;
-        if (ABLATE == 5) { b0 = kf[0]; b1 = kf[0]; }  // skip LDS frag reads
-        else {
-          b0 = read_tr_frag(ldsDOt, 32 * cb + (lane & 31), 16 * (lane >> 5));
-          b1 = read_tr_frag(ldsDOt, 32 * cb + (lane & 31), 32 + 16 * (lane >> 5));
-        }
+        bf16x8_t b0 = read_tr_frag(ldsDOt, 32 * cb + (lane & 31), 16 * (lane >> 5));
+        bf16x8_t b1 = read_tr_frag(ldsDOt, 32 * cb + (lane & 31), 32 + 16 * (lane >> 5));
         dvacc[cb] = mfma_32x32x16_bf16(pf0, b0, dvacc[cb]);
         dvacc[cb] = mfma_32x32x16_bf16(pf1, b1, dvacc[cb]);
       }
@@ -959,27 +787,17 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
         if constexpr (DROP) dpr = ((keep >> r) & 1u) ? dpr * inv_keep : 0.f;
         ds[r] = p[r] * (dpr - deltab[mfma_d_row(lane, r)]) * scale;
       }
-      bf16x8_t df0, df1;
-      if (ABLATE == 4) {
-        asm volatile("" :: "v"(ds[0]), "v"(ds[8]));
-        df0 = kf[0]; df1 = kf[0];
-      } else {
-        df0 = dlayout_to_afrag(ds);
-        df1 = dlayout_to_afrag(ds + 8);
-      }
+      bf16x8_t df0 = dlayout_to_afrag(ds);
+      bf16x8_t df1 = dlayout_to_afrag(ds + 8);
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
-        bf16x8_t b0, b1;
-        if (ABLATE == 5) { b0 = kf[0]; b1 = kf[0]; }
-        else {
-          b0 = read_tr_frag(ldsQt, 32 * cb + (lane & 31), 16 * (lane >> 5));
-          b1 = read_tr_frag(ldsQt, 32 * cb + (lane & 31), 32 + 16 * (lane >> 5));
-        }
+        bf16x8_t b0 = read_tr_frag(ldsQt, 32 * cb + (lane & 31), 16 * (lane >> 5));
+        bf16x8_t b1 = read_tr_frag(ldsQt, 32 * cb + (lane & 31), 32 + 16 * (lane >> 5));
         dkacc[cb] = mfma_32x32x16_bf16(df0, b0, dkacc[cb]);
         dkacc[cb] = mfma_32x32x16_bf16(df1, b1, dkacc[cb]);
       }
     }
-    if (ABLATE != 2 && pre) {  // writes late
+    if (pre) {  // writes late
       u16* bq = base + (buf ^ 1) * TILE;
       qst.write_rm(bq);
       qst.write_tr(bq + 32 * C);
@@ -1039,8 +857,8 @@ __global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dkv_kernel(
 // ===========================================================================
 // DROP: same dP = (dO V^T)oZ and dS as the dkv kernel; registers 4g..4g+3
 // are four consecutive q at this lane's k, one Philox call per group.
-template <int C, int NW, int SPW, int MINW, bool DROP = false>
-__global__ __launch_bounds__(NW * 64, MINW) void attn_bwd_dq_kernel(
+template <int C, int NW, int SPW, bool DROP = false>
+__global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(
     const u16* __restrict__ dO, const u16* __restrict__ q,
     const u16* __restrict__ k, const u16* __restrict__ v,
     const float* __restrict__ lse, const float* __restrict__ delta,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
 
+#include <type_traits>
 #include <vector>
 
 #define CHECK_GPU(x) TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be contiguous GPU tensor")
@@ -15,6 +16,18 @@ static hipStream_t cur_stream() {
 static void launch_check() {
   hipError_t e = hipGetLastError();
   TORCH_CHECK(e == hipSuccess, "HIP launch failed: ", hipGetErrorString(e));
+}
+
+// Launch on the current stream. Dynamic LDS above the 64 KiB default cap
+// (gfx950 has 160 KiB/CU) needs the attribute raised first.
+template <typename... P, typename... A>
+static void launch(void (*kernel)(P...), long grid, int block, size_t smem, A... args) {
+  if (smem > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), smem, cur_stream(),
+                     static_cast<P>(args)...);
+  launch_check();
 }
 
 // ---------------------------------------------------------------------------
@@ -69,18 +82,13 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
 
 // Fused residual add + RMSNorm (weightless, bf16, D % 8 == 0). Launch
 // geometry of rmsnorm_fwd / rmsnorm_bwd: one wave per row, 4 per block.
-#define LAUNCH_BY_ROW_WIDTH(KERNEL, ...)                                        \
-  do {                                                                          \
-    if (D <= 2048)                                                              \
-      hipLaunchKernelGGL((KERNEL<4>), dim3(grid), dim3(256), 0, cur_stream(),   \
-                         __VA_ARGS__);                                          \
-    else if (D <= 4096)                                                         \
-      hipLaunchKernelGGL((KERNEL<8>), dim3(grid), dim3(256), 0, cur_stream(),   \
-                         __VA_ARGS__);                                          \
-    else                                                                        \
-      hipLaunchKernelGGL((KERNEL<0>), dim3(grid), dim3(256), 0, cur_stream(),   \
-                         __VA_ARGS__);                                          \
-  } while (0)
+// f(integral constant): the kernels' template argument for row width D.
+template <typename F>
+static void dispatch_row_width(int D, F&& f) {
+  if (D <= 2048) f(std::integral_constant<int, 4>{});
+  else if (D <= 4096) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 0>{});
+}
 
 std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x, torch::Tensor r, double eps) {
   CHECK_GPU(x); CHECK_GPU(r);
@@ -95,10 +103,11 @@ std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x, torch::Tensor r, dou
   auto invrms = torch::empty({N}, x.options().dtype(torch::kFloat));
   long grid = std::min((N + 3) / 4, (long)8192);
   if (N > 0)
-    LAUNCH_BY_ROW_WIDTH(add_rmsnorm_fwd_bf16, (const u16*)x.data_ptr(),
-                        (const u16*)r.data_ptr(), (u16*)s.data_ptr(),
-                        (u16*)y.data_ptr(), invrms.data_ptr<float>(), N, D, (float)eps);
-  launch_check();
+    dispatch_row_width(D, [&](auto w) {
+      launch(add_rmsnorm_fwd_bf16<decltype(w)::value>, grid, 256, 0,
+             (const u16*)x.data_ptr(), (const u16*)r.data_ptr(), (u16*)s.data_ptr(),
+             (u16*)y.data_ptr(), invrms.data_ptr<float>(), N, D, (float)eps);
+    });
   return {s, y, invrms};
 }
 
@@ -123,49 +132,120 @@ torch::Tensor add_rmsnorm_bwd(c10::optional<torch::Tensor> ds, torch::Tensor dy,
   auto dx = torch::empty_like(s);
   long grid = std::min((N + 3) / 4, (long)8192);
   if (N > 0)
-    LAUNCH_BY_ROW_WIDTH(add_rmsnorm_bwd_bf16, dsp, (const u16*)dy.data_ptr(),
-                        (const u16*)s.data_ptr(), invrms.data_ptr<float>(),
-                        (u16*)dx.data_ptr(), N, D);
-  launch_check();
+    dispatch_row_width(D, [&](auto w) {
+      launch(add_rmsnorm_bwd_bf16<decltype(w)::value>, grid, 256, 0, dsp,
+             (const u16*)dy.data_ptr(), (const u16*)s.data_ptr(),
+             invrms.data_ptr<float>(), (u16*)dx.data_ptr(), N, D);
+    });
   return dx;
 }
-#undef LAUNCH_BY_ROW_WIDTH
 
 // ---------------------------------------------------------------------------
-// The qkv_prep kernels reduce over C/8 lanes with width-(C/8) shuffles and
-// put 64/(C/8) rows in a wave: C/8 must be a power of two that divides 64.
-static void check_qkv_head_dim(int C) {
+// What the qkv_prep kernels read besides the gradients, checked once: the
+// packed projection (B,T,3,H,C) bf16, LN weights (C,) and RoPE tables of at
+// least T rows of C/2, the latter four as contiguous fp32.
+struct PrepInputs {
+  int B, T, H, C;
+  torch::Tensor qw, kw, sin, cos;  // fp32
+};
+static PrepInputs prep_inputs(const torch::Tensor& qkv, const torch::Tensor& qw,
+                              const torch::Tensor& kw, const torch::Tensor& sin_t,
+                              const torch::Tensor& cos_t) {
+  CHECK_GPU(qkv);
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "qkv_prep: qkv must be bf16");
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "qkv_prep: qkv must be (B,T,3,H,C)");
+  int B = qkv.size(0), T = qkv.size(1), H = qkv.size(3), C = qkv.size(4);
+  // The kernels reduce over C/8 lanes with width-(C/8) shuffles and put
+  // 64/(C/8) rows in a wave: C/8 must be a power of two that divides 64.
   TORCH_CHECK(C == 8 || C == 16 || C == 32 || C == 64 || C == 128,
               "qkv_prep: head dim must be 8, 16, 32, 64 or 128 (got ", C, ")");
+  TORCH_CHECK(qw.is_cuda() && kw.is_cuda() && qw.numel() == C && kw.numel() == C,
+              "qkv_prep: weights must be GPU tensors of (C,)");
+  TORCH_CHECK(sin_t.is_cuda() && cos_t.is_cuda() && sin_t.dim() == 2 &&
+              sin_t.size(0) >= T && sin_t.size(1) == C / 2 &&
+              cos_t.sizes() == sin_t.sizes(),
+              "qkv_prep: sin/cos must be GPU tensors of (>= T, C/2)");
+  auto f32 = [](const torch::Tensor& t) { return t.to(torch::kFloat).contiguous(); };
+  return {B, T, H, C, f32(qw), f32(kw), f32(sin_t), f32(cos_t)};
+}
+
+// SLOTS = 3: q, k and the V copy; SLOTS = 2: q and k only (v undefined).
+template <int SLOTS>
+static std::vector<torch::Tensor> prep_fwd(torch::Tensor qkv, torch::Tensor qw,
+                                           torch::Tensor kw, torch::Tensor sin_t,
+                                           torch::Tensor cos_t, double eps) {
+  const PrepInputs in = prep_inputs(qkv, qw, kw, sin_t, cos_t);
+  const int B = in.B, T = in.T, H = in.H, C = in.C;
+  auto opt = qkv.options();
+  auto q = torch::empty({B, H, T, C}, opt);
+  auto k = torch::empty({B, H, T, C}, opt);
+  torch::Tensor v;
+  if (SLOTS == 3) v = torch::empty({B, H, T, C}, opt);
+  auto qstats = torch::empty({B, H, T, 2}, opt.dtype(torch::kFloat));
+  auto kstats = torch::empty({B, H, T, 2}, opt.dtype(torch::kFloat));
+  long nrows = (long)B * T * H * SLOTS;
+  long grid = std::min((nrows + 3) / 4, (long)16384);
+  if (nrows > 0)
+    hipLaunchKernelGGL(qkv_prep_fwd_kernel<SLOTS>, dim3(grid), dim3(256), 0, cur_stream(),
+                       (const u16*)qkv.data_ptr(), in.qw.data_ptr<float>(),
+                       in.kw.data_ptr<float>(), in.sin.data_ptr<float>(),
+                       in.cos.data_ptr<float>(), (u16*)q.data_ptr(), (u16*)k.data_ptr(),
+                       SLOTS == 3 ? (u16*)v.data_ptr() : (u16*)nullptr,
+                       qstats.data_ptr<float>(), kstats.data_ptr<float>(),
+                       B, T, H, C, (float)eps);
+  launch_check();
+  return {q, k, v, qstats, kstats};
+}
+
+// Fills slots 0 and 1 of dqkv, and slot 2 from dv where one is given
+// (otherwise attn_bwd_packed writes it). Returns {dqw, dkw}.
+static std::vector<torch::Tensor> prep_bwd(torch::Tensor dq, torch::Tensor dk,
+                                           const torch::Tensor* dv, torch::Tensor qkv,
+                                           torch::Tensor qw, torch::Tensor kw,
+                                           torch::Tensor sin_t, torch::Tensor cos_t,
+                                           torch::Tensor qstats, torch::Tensor kstats,
+                                           torch::Tensor dqkv) {
+  const PrepInputs in = prep_inputs(qkv, qw, kw, sin_t, cos_t);
+  const int B = in.B, T = in.T, H = in.H, C = in.C;
+  const long n = (long)B * H * T * C;
+  for (const torch::Tensor* g : std::initializer_list<const torch::Tensor*>{&dq, &dk, dv}) {
+    if (!g) continue;
+    CHECK_GPU((*g));
+    TORCH_CHECK(g->scalar_type() == torch::kBFloat16 && g->numel() == n,
+                "qkv_prep_bwd: dq, dk, dv must be bf16 (B,H,T,C)");
+  }
+  CHECK_GPU(qstats); CHECK_GPU(kstats); CHECK_GPU(dqkv);
+  TORCH_CHECK(qstats.scalar_type() == torch::kFloat &&
+              kstats.scalar_type() == torch::kFloat &&
+              qstats.numel() == (long)B * H * T * 2 && kstats.numel() == qstats.numel(),
+              "qkv_prep_bwd: stats must be fp32 (B,H,T,2)");
+  TORCH_CHECK(dqkv.scalar_type() == torch::kBFloat16 && dqkv.sizes() == qkv.sizes(),
+              "qkv_prep_bwd: dqkv must be bf16 with qkv's shape");
+  // One row sequence and grid with or without dv (V rows skipped without):
+  // that keeps the partial sums, hence dqw and dkw, bit-identical.
+  long nrows = (long)B * T * H * 3;
+  int nblocks = (int)std::min((nrows + 3) / 4, (long)4096);
+  auto dqw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
+  auto dkw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
+  size_t smem = 4 * 2 * C * sizeof(float);  // [waves = 256/64][2][C]
+  auto kernel = dv ? qkv_prep_bwd_kernel<true> : qkv_prep_bwd_kernel<false>;
+  if (nrows > 0)
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(256), smem, cur_stream(),
+                       (const u16*)dq.data_ptr(), (const u16*)dk.data_ptr(),
+                       dv ? (const u16*)dv->data_ptr() : (const u16*)nullptr,
+                       (const u16*)qkv.data_ptr(), in.qw.data_ptr<float>(),
+                       in.kw.data_ptr<float>(), in.sin.data_ptr<float>(),
+                       in.cos.data_ptr<float>(), qstats.data_ptr<float>(),
+                       kstats.data_ptr<float>(), (u16*)dqkv.data_ptr(),
+                       dqw_p.data_ptr<float>(), dkw_p.data_ptr<float>(), B, T, H, C);
+  launch_check();
+  return {dqw_p.sum(0).to(qw.scalar_type()), dkw_p.sum(0).to(kw.scalar_type())};
 }
 
 std::vector<torch::Tensor> qkv_prep_fwd(torch::Tensor qkv, torch::Tensor qw,
                                         torch::Tensor kw, torch::Tensor sin_t,
                                         torch::Tensor cos_t, double eps) {
-  CHECK_GPU(qkv);
-  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "qkv must be bf16");
-  int B = qkv.size(0), T = qkv.size(1), H = qkv.size(3), C = qkv.size(4);
-  check_qkv_head_dim(C);
-  auto opt = qkv.options();
-  auto q = torch::empty({B, H, T, C}, opt);
-  auto k = torch::empty({B, H, T, C}, opt);
-  auto v = torch::empty({B, H, T, C}, opt);
-  auto qstats = torch::empty({B, H, T, 2}, opt.dtype(torch::kFloat));
-  auto kstats = torch::empty({B, H, T, 2}, opt.dtype(torch::kFloat));
-  auto qwf = qw.to(torch::kFloat).contiguous();
-  auto kwf = kw.to(torch::kFloat).contiguous();
-  auto sf = sin_t.to(torch::kFloat).contiguous();
-  auto cf = cos_t.to(torch::kFloat).contiguous();
-  long nrows = (long)B * T * H * 3;
-  long grid = std::min((nrows + 3) / 4, (long)16384);
-  hipLaunchKernelGGL(qkv_prep_fwd_kernel<3>, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const u16*)qkv.data_ptr(), qwf.data_ptr<float>(),
-                     kwf.data_ptr<float>(), sf.data_ptr<float>(), cf.data_ptr<float>(),
-                     (u16*)q.data_ptr(), (u16*)k.data_ptr(), (u16*)v.data_ptr(),
-                     qstats.data_ptr<float>(), kstats.data_ptr<float>(),
-                     B, T, H, C, (float)eps);
-  launch_check();
-  return {q, k, v, qstats, kstats};
+  return prep_fwd<3>(qkv, qw, kw, sin_t, cos_t, eps);
 }
 
 std::vector<torch::Tensor> qkv_prep_bwd(torch::Tensor dq, torch::Tensor dk,
@@ -174,80 +254,17 @@ std::vector<torch::Tensor> qkv_prep_bwd(torch::Tensor dq, torch::Tensor dk,
                                         torch::Tensor sin_t, torch::Tensor cos_t,
                                         torch::Tensor qstats, torch::Tensor kstats,
                                         double eps) {
-  CHECK_GPU(dq); CHECK_GPU(dk); CHECK_GPU(dv); CHECK_GPU(qkv);
-  CHECK_GPU(qstats); CHECK_GPU(kstats);
-  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16 &&
-              dq.scalar_type() == torch::kBFloat16 &&
-              dk.scalar_type() == torch::kBFloat16 &&
-              dv.scalar_type() == torch::kBFloat16,
-              "qkv_prep_bwd: qkv, dq, dk, dv must be bf16");
-  TORCH_CHECK(qstats.scalar_type() == torch::kFloat &&
-              kstats.scalar_type() == torch::kFloat,
-              "qkv_prep_bwd: stats must be fp32");
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "qkv_prep_bwd: qkv must be (B,T,3,H,C)");
-  int B = qkv.size(0), T = qkv.size(1), H = qkv.size(3), C = qkv.size(4);
-  check_qkv_head_dim(C);
-  TORCH_CHECK(dq.numel() == (long)B * H * T * C && dk.numel() == dq.numel() &&
-              dv.numel() == dq.numel() && qstats.numel() == (long)B * H * T * 2 &&
-              kstats.numel() == qstats.numel(),
-              "qkv_prep_bwd: dq/dk/dv must be (B,H,T,C) and stats (B,H,T,2)");
   auto dqkv = torch::empty_like(qkv);
-  auto qwf = qw.to(torch::kFloat).contiguous();
-  auto kwf = kw.to(torch::kFloat).contiguous();
-  auto sf = sin_t.to(torch::kFloat).contiguous();
-  auto cf = cos_t.to(torch::kFloat).contiguous();
-  long nrows = (long)B * T * H * 3;
-  int nblocks = (int)std::min((nrows + 3) / 4, (long)4096);
-  auto dqw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
-  auto dkw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
-  size_t smem = 4 * 2 * C * sizeof(float);  // [waves = 256/64][2][C]
-  hipLaunchKernelGGL(qkv_prep_bwd_kernel<true>, dim3(nblocks), dim3(256), smem, cur_stream(),
-                     (const u16*)dq.data_ptr(), (const u16*)dk.data_ptr(),
-                     (const u16*)dv.data_ptr(), (const u16*)qkv.data_ptr(),
-                     qwf.data_ptr<float>(), kwf.data_ptr<float>(),
-                     sf.data_ptr<float>(), cf.data_ptr<float>(),
-                     qstats.data_ptr<float>(), kstats.data_ptr<float>(),
-                     (u16*)dqkv.data_ptr(), dqw_p.data_ptr<float>(),
-                     dkw_p.data_ptr<float>(), B, T, H, C);
-  launch_check();
-  auto dqw = dqw_p.sum(0).to(qw.scalar_type());
-  auto dkw = dkw_p.sum(0).to(kw.scalar_type());
-  return {dqkv, dqw, dkw};
+  auto dw = prep_bwd(dq, dk, &dv, qkv, qw, kw, sin_t, cos_t, qstats, kstats, dqkv);
+  return {dqkv, dw[0], dw[1]};
 }
 
-// Q/K-only variants: no V copy in either direction. The backward fills slots
-// 0 and 1 of a caller-supplied dqkv (slot 2 is written by attn_bwd_packed).
+// Q/K-only variants: no V copy in either direction.
 std::vector<torch::Tensor> qk_prep_fwd(torch::Tensor qkv, torch::Tensor qw,
                                        torch::Tensor kw, torch::Tensor sin_t,
                                        torch::Tensor cos_t, double eps) {
-  CHECK_GPU(qkv);
-  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "qkv must be bf16");
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "qk_prep_fwd: qkv must be (B,T,3,H,C)");
-  int B = qkv.size(0), T = qkv.size(1), H = qkv.size(3), C = qkv.size(4);
-  check_qkv_head_dim(C);
-  TORCH_CHECK(qw.numel() == C && kw.numel() == C, "qk_prep_fwd: weights must be (C,)");
-  TORCH_CHECK(sin_t.numel() == (long)T * (C / 2) && cos_t.numel() == sin_t.numel(),
-              "qk_prep_fwd: sin/cos must be (T, C/2)");
-  auto opt = qkv.options();
-  auto q = torch::empty({B, H, T, C}, opt);
-  auto k = torch::empty({B, H, T, C}, opt);
-  auto qstats = torch::empty({B, H, T, 2}, opt.dtype(torch::kFloat));
-  auto kstats = torch::empty({B, H, T, 2}, opt.dtype(torch::kFloat));
-  auto qwf = qw.to(torch::kFloat).contiguous();
-  auto kwf = kw.to(torch::kFloat).contiguous();
-  auto sf = sin_t.to(torch::kFloat).contiguous();
-  auto cf = cos_t.to(torch::kFloat).contiguous();
-  long nrows = (long)B * T * H * 2;
-  long grid = std::min((nrows + 3) / 4, (long)16384);
-  if (nrows > 0)
-    hipLaunchKernelGGL(qkv_prep_fwd_kernel<2>, dim3(grid), dim3(256), 0, cur_stream(),
-                       (const u16*)qkv.data_ptr(), qwf.data_ptr<float>(),
-                       kwf.data_ptr<float>(), sf.data_ptr<float>(), cf.data_ptr<float>(),
-                       (u16*)q.data_ptr(), (u16*)k.data_ptr(), (u16*)nullptr,
-                       qstats.data_ptr<float>(), kstats.data_ptr<float>(),
-                       B, T, H, C, (float)eps);
-  launch_check();
-  return {q, k, qstats, kstats};
+  auto r = prep_fwd<2>(qkv, qw, kw, sin_t, cos_t, eps);
+  return {r[0], r[1], r[3], r[4]};
 }
 
 std::vector<torch::Tensor> qk_prep_bwd(torch::Tensor dq, torch::Tensor dk,
@@ -255,51 +272,7 @@ std::vector<torch::Tensor> qk_prep_bwd(torch::Tensor dq, torch::Tensor dk,
                                        torch::Tensor kw, torch::Tensor sin_t,
                                        torch::Tensor cos_t, torch::Tensor qstats,
                                        torch::Tensor kstats, torch::Tensor dqkv) {
-  CHECK_GPU(dq); CHECK_GPU(dk); CHECK_GPU(qkv); CHECK_GPU(dqkv);
-  CHECK_GPU(qstats); CHECK_GPU(kstats);
-  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16 &&
-              dq.scalar_type() == torch::kBFloat16 &&
-              dk.scalar_type() == torch::kBFloat16 &&
-              dqkv.scalar_type() == torch::kBFloat16,
-              "qk_prep_bwd: qkv, dq, dk, dqkv must be bf16");
-  TORCH_CHECK(qstats.scalar_type() == torch::kFloat &&
-              kstats.scalar_type() == torch::kFloat,
-              "qk_prep_bwd: stats must be fp32");
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "qk_prep_bwd: qkv must be (B,T,3,H,C)");
-  TORCH_CHECK(dqkv.sizes() == qkv.sizes(), "qk_prep_bwd: dqkv must have qkv's shape");
-  int B = qkv.size(0), T = qkv.size(1), H = qkv.size(3), C = qkv.size(4);
-  check_qkv_head_dim(C);
-  TORCH_CHECK(dq.numel() == (long)B * H * T * C && dk.numel() == dq.numel() &&
-              qstats.numel() == (long)B * H * T * 2 &&
-              kstats.numel() == qstats.numel(),
-              "qk_prep_bwd: dq/dk must be (B,H,T,C) and stats (B,H,T,2)");
-  TORCH_CHECK(qw.numel() == C && kw.numel() == C, "qk_prep_bwd: weights must be (C,)");
-  TORCH_CHECK(sin_t.numel() == (long)T * (C / 2) && cos_t.numel() == sin_t.numel(),
-              "qk_prep_bwd: sin/cos must be (T, C/2)");
-  auto qwf = qw.to(torch::kFloat).contiguous();
-  auto kwf = kw.to(torch::kFloat).contiguous();
-  auto sf = sin_t.to(torch::kFloat).contiguous();
-  auto cf = cos_t.to(torch::kFloat).contiguous();
-  // Same row sequence and grid as qkv_prep_bwd (V rows skipped): that keeps
-  // the partial sums, hence dqw and dkw, bit-identical to it.
-  long nrows = (long)B * T * H * 3;
-  int nblocks = (int)std::min((nrows + 3) / 4, (long)4096);
-  auto dqw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
-  auto dkw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
-  size_t smem = 4 * 2 * C * sizeof(float);  // [waves = 256/64][2][C]
-  if (nrows > 0)
-    hipLaunchKernelGGL(qkv_prep_bwd_kernel<false>, dim3(nblocks), dim3(256), smem,
-                       cur_stream(), (const u16*)dq.data_ptr(), (const u16*)dk.data_ptr(),
-                       (const u16*)nullptr, (const u16*)qkv.data_ptr(),
-                       qwf.data_ptr<float>(), kwf.data_ptr<float>(),
-                       sf.data_ptr<float>(), cf.data_ptr<float>(),
-                       qstats.data_ptr<float>(), kstats.data_ptr<float>(),
-                       (u16*)dqkv.data_ptr(), dqw_p.data_ptr<float>(),
-                       dkw_p.data_ptr<float>(), B, T, H, C);
-  launch_check();
-  auto dqw = dqw_p.sum(0).to(qw.scalar_type());
-  auto dkw = dkw_p.sum(0).to(kw.scalar_type());
-  return {dqw, dkw};
+  return prep_bwd(dq, dk, nullptr, qkv, qw, kw, sin_t, cos_t, qstats, kstats, dqkv);
 }
 
 // ---------------------------------------------------------------------------
@@ -368,6 +341,7 @@ static AttnStrides strides_qkv_slot(int H, int T, int C) {  // one slot of (B,T,
   return {(long)T * 3 * H * C, (long)C, 3 * H * C};
 }
 
+// Argument checks shared by every attention entry point.
 static void check_attn_qk(const torch::Tensor& q, const torch::Tensor& k) {
   CHECK_GPU(q); CHECK_GPU(k);
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
@@ -376,6 +350,12 @@ static void check_attn_qk(const torch::Tensor& q, const torch::Tensor& k) {
   TORCH_CHECK(q.size(2) % 128 == 0, "attn: T % 128 == 0 required (got ", q.size(2), ")");
   TORCH_CHECK(q.size(3) == 64 || q.size(3) == 128,
               "attn: head dim 64 or 128 (got ", q.size(3), ")");
+}
+static void check_attn_bhtc(const torch::Tensor& q, const torch::Tensor& x,
+                            const char* name) {
+  CHECK_GPU(x);
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.sizes() == q.sizes(),
+              "attn: ", name, " must be bf16 (B,H,T,C) like q");
 }
 // qkv (B,T,3,H,C) that q, k (B,H,T,C) were made from.
 static void check_attn_packed(const torch::Tensor& q, const torch::Tensor& qkv,
@@ -394,366 +374,174 @@ static void check_attn_bthc(const torch::Tensor& q, const torch::Tensor& x,
               x.size(2) == q.size(1) && x.size(3) == q.size(3),
               "attn: ", name, " must be (B,T,H,C) matching q (B,H,T,C)");
 }
-
-// One launcher for every layout: v is read and o written through strides.
-static void attn_fwd_launch(torch::Tensor q, torch::Tensor k, const u16* vp,
-                            AttnStrides sv, u16* op, AttnStrides so,
-                            torch::Tensor lse) {
-  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
-  // Measured best: 8-wave WGs at 2 waves/SIMD, SPW=1. The SPW=2
-  // mirrored-strip variant (1 wave/SIMD for C=128) and 3-waves/SIMD were
-  // both measured slower — SQ_WAIT is memory-wait dominated, so wave
-  // co-residency (TLP) matters most. Fallback to 4 waves for small T.
-  const int NW = (T % 256 == 0) ? 8 : 4;
-  const int SPW = 1;
-  long grid = (long)B * H * (T / (NW * 32 * SPW));
-  size_t smem = std::max((size_t)(4 * 32 * C * 2), (size_t)(NW * 32 * 32 * 4));
-#define LAUNCH_FWD(CC, NN, SS, MM)                                              \
-  hipLaunchKernelGGL((attn_fwd_kernel<CC, NN, SS, MM>), dim3(grid),             \
-                     dim3(NN * 64),                                             \
-                     smem, cur_stream(), (const u16*)q.data_ptr(),              \
-                     (const u16*)k.data_ptr(), vp,        \
-                     op, lse.data_ptr<float>(), B, H, T, sv, so)
-  // depth-2 prefetch single-tile kernel (4 LDS buffers, loads 2 tiles
-  // ahead): opt-in A/B via MIDGPT_ATTN_FWD_D2=1
-  static const bool fwd_d2 = getenv("MIDGPT_ATTN_FWD_D2") != nullptr;
-  if (fwd_d2 && NW == 8) {
-    size_t smem_d2 = std::max((size_t)(8 * 32 * C * 2), (size_t)(NW * 32 * 32 * 4));
-    if (C == 128)
-      hipLaunchKernelGGL((attn_fwd_d2_kernel<128, 8>), dim3(grid), dim3(512),
-                         smem_d2, cur_stream(), (const u16*)q.data_ptr(),
-                         (const u16*)k.data_ptr(), vp,
-                         op, lse.data_ptr<float>(), B, H, T, sv, so);
-    else
-      hipLaunchKernelGGL((attn_fwd_d2_kernel<64, 8>), dim3(grid), dim3(512),
-                         smem_d2, cur_stream(), (const u16*)q.data_ptr(),
-                         (const u16*)k.data_ptr(), vp,
-                         op, lse.data_ptr<float>(), B, H, T, sv, so);
-    launch_check();
-    return;
-  }
-  // paired-tile kernel (one merged rescale per 64 k): measured +4% at
-  // C=128, -4% at C=64 -> default for C=128 only (MIDGPT_ATTN_FWD2=1
-  // forces it everywhere, MIDGPT_ATTN_FWD1=1 disables).
-  static const bool fwd2_force = getenv("MIDGPT_ATTN_FWD2") != nullptr;
-  static const bool fwd1_force = getenv("MIDGPT_ATTN_FWD1") != nullptr;
-  const bool fwd2 = !fwd1_force && (fwd2_force || C == 128);
-  if (fwd2 && NW == 8) {
-    size_t smem2 = std::max((size_t)(8 * 32 * C * 2), (size_t)(NW * 32 * 32 * 4));
-#define LAUNCH_FWD2(CC)                                                         \
-    do {                                                                        \
-      if (smem2 > 64 * 1024)                                                    \
-        hipFuncSetAttribute(                                                    \
-            reinterpret_cast<const void*>(&attn_fwd2_kernel<CC, 8>),            \
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);            \
-      hipLaunchKernelGGL((attn_fwd2_kernel<CC, 8>), dim3(grid), dim3(512),      \
-                         smem2, cur_stream(), (const u16*)q.data_ptr(),         \
-                         (const u16*)k.data_ptr(), vp,    \
-                         op, lse.data_ptr<float>(), B, H, T, sv, so);   \
-    } while (0)
-    if (C == 128) LAUNCH_FWD2(128); else LAUNCH_FWD2(64);
-#undef LAUNCH_FWD2
-    launch_check();
-    return;
-  }
-  static const bool minw3 = getenv("MIDGPT_ATTN_FWD_MINW3") != nullptr;
-  if (C == 128 && NW == 8 && minw3) LAUNCH_FWD(128, 8, 1, 3);
-  else if (C == 128 && NW == 8) LAUNCH_FWD(128, 8, 1, 2);
-  else if (C == 128) LAUNCH_FWD(128, 4, 1, 2);
-  else if (NW == 8 && minw3) LAUNCH_FWD(64, 8, 1, 3);
-  else if (NW == 8) LAUNCH_FWD(64, 8, 1, 2);
-  else LAUNCH_FWD(64, 4, 1, 2);
-#undef LAUNCH_FWD
-  launch_check();
-  return;
+static void check_attn_lse(const torch::Tensor& q, const torch::Tensor& lse) {
+  CHECK_GPU(lse);
+  TORCH_CHECK(lse.scalar_type() == torch::kFloat &&
+              lse.numel() == q.size(0) * q.size(1) * q.size(2),
+              "attn: lse must be fp32 (B,H,T)");
 }
 
-std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v) {
-  CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v);
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn: bf16 required");
-  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
-  TORCH_CHECK(T % 128 == 0, "attn: T % 128 == 0 required (got ", T, ")");
-  TORCH_CHECK(C == 64 || C == 128, "attn: head dim 64 or 128 (got ", C, ")");
-  auto o = torch::empty_like(q);
-  auto lse = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
-  const AttnStrides st = strides_bhtc(H, T, C);
-  attn_fwd_launch(q, k, (const u16*)v.data_ptr(), st, (u16*)o.data_ptr(), st, lse);
-  return {o, lse};
-}
-
-// One launcher for every layout: dO, v, o are read and dv written through
-// strides. Returns {dq, dk} (packed (B,H,T,C)).
-static std::vector<torch::Tensor> attn_bwd_launch(
-    const u16* dop, AttnStrides sdo, torch::Tensor q, torch::Tensor k,
-    const u16* vp, AttnStrides sv, const u16* op, AttnStrides so,
-    torch::Tensor lse, u16* dvp, AttnStrides sdv, u16* do_copy = nullptr) {
-  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
-  long N = (long)B * H * T;
-  auto delta = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
-  TORCH_CHECK(N < (1L << 31), "attn: B*H*T must be below 2^31");
-  long dgrid = std::min((N + 3) / 4, (long)8192);
-  hipLaunchKernelGGL(attn_delta_kernel, dim3(dgrid), dim3(256), 0, cur_stream(),
-                     dop, op,
-                     delta.data_ptr<float>(), N, C, H, T, sdo, so, do_copy,
-                     (int)(sdo.h < sdo.r));
-  launch_check();
-  if (do_copy) {  // the delta kernel left dO as packed (B,H,T,C) there
-    dop = do_copy;
-    sdo = strides_bhtc(H, T, C);
-  }
-  auto dq = torch::empty_like(q);
-  auto dk = torch::empty_like(k);
-  static const bool dkv4 = getenv("MIDGPT_ATTN_DKV_NW4") != nullptr;
-  const int NW_A = dkv4 ? 4 : ((T % 256 == 0) ? 8 : 4);  // dkv geometry
-  const int NW_B = NW_A;                     // dq geometry
-  const int SPW = 1;
-  long grid_a = (long)B * H * (T / (NW_A * 32));
-  long grid_b = (long)B * H * (T / (NW_B * 32 * SPW));
-  // double-buffered staging: dkv = 2x(Q,Qt,dO,dOt) + lse/delta;
-  // dq = 2x(K,V,Kt) + per-wave dS. Above the 64 KiB default dynamic-LDS
-  // cap (gfx950 has 160 KiB/CU) -> raise the attribute.
-  size_t smem_a = std::max((size_t)(2 * 4 * 32 * C) * 2 + 2 * 64 * 4,
-                           (size_t)(NW_A * 32 * 32 * 4));
-  size_t smem_b = std::max((size_t)(2 * 3 * 32 * C) * 2 + NW_B * 32 * 32 * 2,
-                           (size_t)(NW_B * 32 * 32 * 4));
-#define LAUNCH_BWD(CC, NA, NB, SS, MM)                                          \
-  do {                                                                          \
-    if (smem_a > 64 * 1024)                                                     \
-      hipFuncSetAttribute(                                                      \
-          reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<CC, NA, 0>),       \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_a);             \
-    if (smem_b > 64 * 1024)                                                     \
-      hipFuncSetAttribute(                                                      \
-          reinterpret_cast<const void*>(&attn_bwd_dq_kernel<CC, NB, SS, MM>),   \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_b);             \
-    static const char* abl = getenv("MIDGPT_DKV_ABLATE");                      \
-    if (abl && abl[0] == '1')                                                   \
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NA, 1>), dim3(grid_a),        \
-                         dim3(NA * 64), smem_a, cur_stream(),                   \
-                         dop, (const u16*)q.data_ptr(),   \
-                         (const u16*)k.data_ptr(), vp,    \
-                         lse.data_ptr<float>(), delta.data_ptr<float>(),        \
-                         (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);    \
-    else if (abl && abl[0] == '3')                                              \
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NA, 3>), dim3(grid_a),        \
-                         dim3(NA * 64), smem_a, cur_stream(),                   \
-                         dop, (const u16*)q.data_ptr(),   \
-                         (const u16*)k.data_ptr(), vp,    \
-                         lse.data_ptr<float>(), delta.data_ptr<float>(),        \
-                         (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);    \
-    else if (abl && abl[0] == '4')                                              \
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NA, 4>), dim3(grid_a),        \
-                         dim3(NA * 64), smem_a, cur_stream(),                   \
-                         dop, (const u16*)q.data_ptr(),   \
-                         (const u16*)k.data_ptr(), vp,    \
-                         lse.data_ptr<float>(), delta.data_ptr<float>(),        \
-                         (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);    \
-    else if (abl && abl[0] == '5')                                              \
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NA, 5>), dim3(grid_a),        \
-                         dim3(NA * 64), smem_a, cur_stream(),                   \
-                         dop, (const u16*)q.data_ptr(),   \
-                         (const u16*)k.data_ptr(), vp,    \
-                         lse.data_ptr<float>(), delta.data_ptr<float>(),        \
-                         (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);    \
-    else if (abl && abl[0] == '2')                                              \
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NA, 2>), dim3(grid_a),        \
-                         dim3(NA * 64), smem_a, cur_stream(),                   \
-                         dop, (const u16*)q.data_ptr(),   \
-                         (const u16*)k.data_ptr(), vp,    \
-                         lse.data_ptr<float>(), delta.data_ptr<float>(),        \
-                         (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);    \
-    else                                                                        \
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NA, 0>), dim3(grid_a),        \
-                         dim3(NA * 64), smem_a, cur_stream(),                   \
-                         dop, (const u16*)q.data_ptr(),   \
-                         (const u16*)k.data_ptr(), vp,    \
-                         lse.data_ptr<float>(), delta.data_ptr<float>(),        \
-                         (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);    \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<CC, NB, SS, MM>), dim3(grid_b),      \
-                       dim3(NB * 64),                                           \
-                       smem_b, cur_stream(), dop,         \
-                       (const u16*)q.data_ptr(), (const u16*)k.data_ptr(),      \
-                       vp, lse.data_ptr<float>(),         \
-                       delta.data_ptr<float>(), (u16*)dq.data_ptr(), B, H, T, sdo, sv);  \
-  } while (0)
-  static const bool bwd_minw3 = getenv("MIDGPT_ATTN_BWD_MINW3") != nullptr;
-  if (C == 64 && NW_A == 8 && bwd_minw3 && !getenv("MIDGPT_DKV_ABLATE")) {
-    // squeeze to 3 waves/SIMD (K frags re-read from L2; compiler caps
-    // VGPRs at 168) — A/B experiment for the 124M config
-    if (smem_a > 64 * 1024)
-      hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<64, 8, 0, 3>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_a);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, 8, 0, 3>), dim3(grid_a),
-                       dim3(512), smem_a, cur_stream(),
-                       dop, (const u16*)q.data_ptr(),
-                       (const u16*)k.data_ptr(), vp,
-                       lse.data_ptr<float>(), delta.data_ptr<float>(),
-                       (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv);
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 8, 1, 3>), dim3(grid_b),
-                       dim3(512), smem_b, cur_stream(),
-                       dop, (const u16*)q.data_ptr(),
-                       (const u16*)k.data_ptr(), vp,
-                       lse.data_ptr<float>(), delta.data_ptr<float>(),
-                       (u16*)dq.data_ptr(), B, H, T, sdo, sv);
-    launch_check();
-    return {dq, dk};
-  }
-  if (C == 128 && NW_A == 8) LAUNCH_BWD(128, 8, 8, 1, 2);
-  else if (C == 128) LAUNCH_BWD(128, 4, 4, 1, 2);
-  else if (NW_B == 8) LAUNCH_BWD(64, 8, 8, 1, 2);
-  else LAUNCH_BWD(64, 4, 4, 1, 2);
-#undef LAUNCH_BWD
-  launch_check();
-  return {dq, dk};
-}
-
-std::vector<torch::Tensor> attn_bwd(torch::Tensor dO, torch::Tensor q, torch::Tensor k,
-                                    torch::Tensor v, torch::Tensor o, torch::Tensor lse) {
-  CHECK_GPU(dO); CHECK_GPU(q);
-  int H = q.size(1), T = q.size(2), C = q.size(3);
-  auto dv = torch::empty_like(v);
-  const AttnStrides st = strides_bhtc(H, T, C);
-  auto r = attn_bwd_launch((const u16*)dO.data_ptr(), st, q, k,
-                           (const u16*)v.data_ptr(), st, (const u16*)o.data_ptr(), st,
-                           lse, (u16*)dv.data_ptr(), st);
-  return {r[0], r[1], dv};
-}
-
-// ---------------------------------------------------------------------------
-// Attention with in-kernel dropout (philox.h). Fixed dispatch: the SPW=1,
-// 2-waves/SIMD single-tile kernels with DROP=true, NW from T as above; none
-// of the experiment environment switches apply here.
+// In-kernel dropout (philox.h). Without it the kernels (DROP = false) take
+// the neutral values and ignore them.
 struct DropArgs {
-  uint32_t seed_lo, seed_hi, thr;
-  float inv_keep;
+  uint32_t seed_lo = 0, seed_hi = 0, thr = 0;
+  float inv_keep = 1.f;
 };
+using MaybeDrop = c10::optional<DropArgs>;
 static DropArgs drop_args(double p, int64_t seed) {
   TORCH_CHECK(p > 0.0 && p < 1.0, "attn dropout: 0 < p < 1 required (got ", p, ")");
   const uint64_t s = (uint64_t)seed;
   return {(uint32_t)s, (uint32_t)(s >> 32), attn_drop_threshold(p),
           (float)(1.0 / (1.0 - p))};
 }
+static MaybeDrop drop_if(double p, int64_t seed) {  // p == 0: no dropout
+  return p > 0.0 ? MaybeDrop(drop_args(p, seed)) : MaybeDrop();
+}
 
-static void attn_fwd_dropout_launch(torch::Tensor q, torch::Tensor k, const u16* vp,
-                                    AttnStrides sv, u16* op, AttnStrides so,
-                                    torch::Tensor lse, const DropArgs& d) {
+// f(C, NW, DROP) as integral constants, for head dim 64|128 and 4|8 waves.
+template <typename F>
+static void dispatch_attn(int C, int NW, bool drop, F&& f) {
+  auto on_drop = [&](auto c, auto nw) {
+    if (drop) f(c, nw, std::true_type{});
+    else f(c, nw, std::false_type{});
+  };
+  using c64 = std::integral_constant<int, 64>;
+  using c128 = std::integral_constant<int, 128>;
+  using w4 = std::integral_constant<int, 4>;
+  using w8 = std::integral_constant<int, 8>;
+  if (C == 128 && NW == 8) on_drop(c128{}, w8{});
+  else if (C == 128) on_drop(c128{}, w4{});
+  else if (NW == 8) on_drop(c64{}, w8{});
+  else on_drop(c64{}, w4{});
+}
+
+// One forward launcher for every layout: v is read and o written through
+// strides. Measured best: 8-wave workgroups at 2 waves/SIMD with one strip
+// per wave, SPW = 1 (the kernels wait on memory, so wave co-residency matters
+// most); 4 waves for T % 256 != 0.
+// The paired-tile kernel is +4% at C=128 and -4% at C=64: C=128 only.
+static void attn_fwd_launch(torch::Tensor q, torch::Tensor k, const u16* vp,
+                            AttnStrides sv, u16* op, AttnStrides so,
+                            torch::Tensor lse, const MaybeDrop& drop) {
   int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
   const int NW = (T % 256 == 0) ? 8 : 4;
-  long grid = (long)B * H * (T / (NW * 32));
-  size_t smem = std::max((size_t)(4 * 32 * C * 2), (size_t)(NW * 32 * 32 * 4));
-#define LAUNCH_FWD_DROP(CC, NN)                                                 \
-  hipLaunchKernelGGL((attn_fwd_kernel<CC, NN, 1, 2, true>), dim3(grid),         \
-                     dim3(NN * 64), smem, cur_stream(),                         \
-                     (const u16*)q.data_ptr(), (const u16*)k.data_ptr(),        \
-                     vp, op,              \
-                     lse.data_ptr<float>(), B, H, T, sv, so, d.seed_lo, d.seed_hi,      \
-                     d.thr, d.inv_keep)
-  if (C == 128 && NW == 8) LAUNCH_FWD_DROP(128, 8);
-  else if (C == 128) LAUNCH_FWD_DROP(128, 4);
-  else if (NW == 8) LAUNCH_FWD_DROP(64, 8);
-  else LAUNCH_FWD_DROP(64, 4);
-#undef LAUNCH_FWD_DROP
-  launch_check();
-  return;
+  const long grid = (long)B * H * (T / (NW * 32));
+  const DropArgs d = drop.value_or(DropArgs{});
+  const u16 *qp = (const u16*)q.data_ptr(), *kp = (const u16*)k.data_ptr();
+  float* lsep = lse.data_ptr<float>();
+  dispatch_attn(C, NW, drop.has_value(), [&](auto c, auto nw, auto dr) {
+    constexpr int CC = decltype(c)::value, NN = decltype(nw)::value;
+    constexpr bool DROP = decltype(dr)::value;
+    constexpr bool PAIRED = CC == 128 && NN == 8 && !DROP;
+    // K and V^T tiles, double-buffered (two tiles each when paired); the
+    // epilogue reuses the region as [NW][32*32] fp32.
+    const size_t smem = std::max((size_t)((PAIRED ? 8 : 4) * 32 * CC * 2),
+                                 (size_t)(NN * 32 * 32 * 4));
+    if constexpr (PAIRED)
+      launch(attn_fwd2_kernel<CC, NN>, grid, NN * 64, smem, qp, kp, vp, op, lsep,
+             B, H, T, sv, so);
+    else
+      launch(attn_fwd_kernel<CC, NN, 1, DROP>, grid, NN * 64, smem, qp, kp, vp, op, lsep,
+             B, H, T, sv, so, d.seed_lo, d.seed_hi, d.thr, d.inv_keep);
+  });
 }
 
-std::vector<torch::Tensor> attn_fwd_dropout(torch::Tensor q, torch::Tensor k,
-                                            torch::Tensor v, double p, int64_t seed) {
-  CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v);
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn: bf16 required");
-  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
-  TORCH_CHECK(T % 128 == 0, "attn: T % 128 == 0 required (got ", T, ")");
-  TORCH_CHECK(C == 64 || C == 128, "attn: head dim 64 or 128 (got ", C, ")");
-  const DropArgs d = drop_args(p, seed);
-  auto o = torch::empty_like(q);
-  auto lse = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
-  const AttnStrides st = strides_bhtc(H, T, C);
-  attn_fwd_dropout_launch(q, k, (const u16*)v.data_ptr(), st, (u16*)o.data_ptr(), st,
-                          lse, d);
-  return {o, lse};
-}
-
-static std::vector<torch::Tensor> attn_bwd_dropout_launch(
+// One backward launcher for every layout: dO, v, o are read and dv written
+// through strides. do_copy: see attn_bwd_packed. Returns {dq, dk} (B,H,T,C).
+static std::vector<torch::Tensor> attn_bwd_launch(
     const u16* dop, AttnStrides sdo, torch::Tensor q, torch::Tensor k,
     const u16* vp, AttnStrides sv, const u16* op, AttnStrides so,
-    torch::Tensor lse, u16* dvp, AttnStrides sdv, const DropArgs& d,
+    torch::Tensor lse, u16* dvp, AttnStrides sdv, const MaybeDrop& drop,
     u16* do_copy = nullptr) {
   int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
   long N = (long)B * H * T;
   auto delta = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
   TORCH_CHECK(N < (1L << 31), "attn: B*H*T must be below 2^31");
   long dgrid = std::min((N + 3) / 4, (long)8192);
-  hipLaunchKernelGGL(attn_delta_kernel, dim3(dgrid), dim3(256), 0, cur_stream(),
-                     dop, op,
-                     delta.data_ptr<float>(), N, C, H, T, sdo, so, do_copy,
-                     (int)(sdo.h < sdo.r));
-  launch_check();
+  launch(attn_delta_kernel, dgrid, 256, 0, dop, op, delta.data_ptr<float>(), N, C, H, T,
+         sdo, so, do_copy, (int)(sdo.h < sdo.r));
   if (do_copy) {  // the delta kernel left dO as packed (B,H,T,C) there
     dop = do_copy;
     sdo = strides_bhtc(H, T, C);
   }
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
-  const int NW = (T % 256 == 0) ? 8 : 4;
-  long grid = (long)B * H * (T / (NW * 32));
-  size_t smem_a = std::max((size_t)(2 * 4 * 32 * C) * 2 + 2 * 64 * 4,
-                           (size_t)(NW * 32 * 32 * 4));
-  size_t smem_b = std::max((size_t)(2 * 3 * 32 * C) * 2 + NW * 32 * 32 * 2,
-                           (size_t)(NW * 32 * 32 * 4));
-#define LAUNCH_BWD_DROP(CC, NN)                                                 \
-  do {                                                                          \
-    if (smem_a > 64 * 1024)                                                     \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(                        \
-                              &attn_bwd_dkv_kernel<CC, NN, 0, 2, true>),        \
-                          hipFuncAttributeMaxDynamicSharedMemorySize,           \
-                          (int)smem_a);                                         \
-    if (smem_b > 64 * 1024)                                                     \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(                        \
-                              &attn_bwd_dq_kernel<CC, NN, 1, 2, true>),         \
-                          hipFuncAttributeMaxDynamicSharedMemorySize,           \
-                          (int)smem_b);                                         \
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<CC, NN, 0, 2, true>), dim3(grid),   \
-                       dim3(NN * 64), smem_a, cur_stream(),                     \
-                       dop, (const u16*)q.data_ptr(),     \
-                       (const u16*)k.data_ptr(), vp,      \
-                       lse.data_ptr<float>(), delta.data_ptr<float>(),          \
-                       (u16*)dk.data_ptr(), dvp, B, H, T,       \
-                       sdo, sv, sdv, d.seed_lo, d.seed_hi, d.thr, d.inv_keep);                \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<CC, NN, 1, 2, true>), dim3(grid),    \
-                       dim3(NN * 64), smem_b, cur_stream(),                     \
-                       dop, (const u16*)q.data_ptr(),     \
-                       (const u16*)k.data_ptr(), vp,      \
-                       lse.data_ptr<float>(), delta.data_ptr<float>(),          \
-                       (u16*)dq.data_ptr(), B, H, T, sdo, sv, d.seed_lo, d.seed_hi,      \
-                       d.thr, d.inv_keep);                                      \
-  } while (0)
-  if (C == 128 && NW == 8) LAUNCH_BWD_DROP(128, 8);
-  else if (C == 128) LAUNCH_BWD_DROP(128, 4);
-  else if (NW == 8) LAUNCH_BWD_DROP(64, 8);
-  else LAUNCH_BWD_DROP(64, 4);
-#undef LAUNCH_BWD_DROP
-  launch_check();
+  // MIDGPT_ATTN_DKV_NW4=1 (read once): 4-wave workgroups for the undropped
+  // dkv and dq kernels at every T. Faster at C=64, slower at C=128
+  // (profiles/launch_refactor.md).
+  static const bool nw4 = getenv("MIDGPT_ATTN_DKV_NW4") != nullptr;
+  const int NW = (T % 256 == 0 && !(nw4 && !drop)) ? 8 : 4;
+  const long grid = (long)B * H * (T / (NW * 32));
+  const DropArgs d = drop.value_or(DropArgs{});
+  const u16 *qp = (const u16*)q.data_ptr(), *kp = (const u16*)k.data_ptr();
+  const float *lsep = lse.data_ptr<float>(), *deltap = delta.data_ptr<float>();
+  dispatch_attn(C, NW, drop.has_value(), [&](auto c, auto nw, auto dr) {
+    constexpr int CC = decltype(c)::value, NN = decltype(nw)::value;
+    constexpr bool DROP = decltype(dr)::value;
+    // double-buffered staging: dkv = 2x(Q,Qt,dO,dOt) + lse/delta;
+    // dq = 2x(K,V,Kt) + per-wave dS; both reused as [NW][32*32] fp32.
+    const size_t smem_dkv = std::max((size_t)(2 * 4 * 32 * CC) * 2 + 2 * 64 * 4,
+                                     (size_t)(NN * 32 * 32 * 4));
+    const size_t smem_dq = std::max((size_t)(2 * 3 * 32 * CC) * 2 + NN * 32 * 32 * 2,
+                                    (size_t)(NN * 32 * 32 * 4));
+    launch(attn_bwd_dkv_kernel<CC, NN, DROP>, grid, NN * 64, smem_dkv, dop, qp, kp, vp,
+           lsep, deltap, (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv,
+           d.seed_lo, d.seed_hi, d.thr, d.inv_keep);
+    launch(attn_bwd_dq_kernel<CC, NN, 1, DROP>, grid, NN * 64, smem_dq, dop, qp, kp, vp,
+           lsep, deltap, (u16*)dq.data_ptr(), B, H, T, sdo, sv,
+           d.seed_lo, d.seed_hi, d.thr, d.inv_keep);
+  });
   return {dq, dk};
 }
 
+// ---------------------------------------------------------------------------
+// Entry points, (B,H,T,C) throughout.
+static std::vector<torch::Tensor> attn_fwd_bhtc(torch::Tensor q, torch::Tensor k,
+                                                torch::Tensor v, const MaybeDrop& drop) {
+  check_attn_qk(q, k);
+  check_attn_bhtc(q, v, "v");
+  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
+  auto o = torch::empty_like(q);
+  auto lse = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
+  const AttnStrides st = strides_bhtc(H, T, C);
+  attn_fwd_launch(q, k, (const u16*)v.data_ptr(), st, (u16*)o.data_ptr(), st, lse, drop);
+  return {o, lse};
+}
+
+static std::vector<torch::Tensor> attn_bwd_bhtc(torch::Tensor dO, torch::Tensor q,
+                                                torch::Tensor k, torch::Tensor v,
+                                                torch::Tensor o, torch::Tensor lse,
+                                                const MaybeDrop& drop) {
+  check_attn_qk(q, k);
+  check_attn_bhtc(q, v, "v");
+  check_attn_bhtc(q, o, "o");
+  check_attn_bhtc(q, dO, "dO");
+  check_attn_lse(q, lse);
+  int H = q.size(1), T = q.size(2), C = q.size(3);
+  auto dv = torch::empty_like(v);
+  const AttnStrides st = strides_bhtc(H, T, C);
+  auto r = attn_bwd_launch((const u16*)dO.data_ptr(), st, q, k, (const u16*)v.data_ptr(),
+                           st, (const u16*)o.data_ptr(), st, lse, (u16*)dv.data_ptr(), st,
+                           drop);
+  return {r[0], r[1], dv};
+}
+
+std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v) {
+  return attn_fwd_bhtc(q, k, v, MaybeDrop());
+}
+std::vector<torch::Tensor> attn_bwd(torch::Tensor dO, torch::Tensor q, torch::Tensor k,
+                                    torch::Tensor v, torch::Tensor o, torch::Tensor lse) {
+  return attn_bwd_bhtc(dO, q, k, v, o, lse, MaybeDrop());
+}
+std::vector<torch::Tensor> attn_fwd_dropout(torch::Tensor q, torch::Tensor k,
+                                            torch::Tensor v, double p, int64_t seed) {
+  return attn_fwd_bhtc(q, k, v, drop_args(p, seed));
+}
 std::vector<torch::Tensor> attn_bwd_dropout(torch::Tensor dO, torch::Tensor q,
                                             torch::Tensor k, torch::Tensor v,
                                             torch::Tensor o, torch::Tensor lse,
                                             double p, int64_t seed) {
-  CHECK_GPU(dO); CHECK_GPU(q); CHECK_GPU(k); CHECK_GPU(v); CHECK_GPU(o); CHECK_GPU(lse);
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn: bf16 required");
-  int H = q.size(1), T = q.size(2), C = q.size(3);
-  TORCH_CHECK(T % 128 == 0, "attn: T % 128 == 0 required (got ", T, ")");
-  TORCH_CHECK(C == 64 || C == 128, "attn: head dim 64 or 128 (got ", C, ")");
-  const DropArgs d = drop_args(p, seed);
-  auto dv = torch::empty_like(v);
-  const AttnStrides st = strides_bhtc(H, T, C);
-  auto r = attn_bwd_dropout_launch((const u16*)dO.data_ptr(), st, q, k,
-                                   (const u16*)v.data_ptr(), st,
-                                   (const u16*)o.data_ptr(), st, lse,
-                                   (u16*)dv.data_ptr(), st, d);
-  return {r[0], r[1], dv};
+  return attn_bwd_bhtc(dO, q, k, v, o, lse, drop_args(p, seed));
 }
 
 // ---------------------------------------------------------------------------
@@ -770,9 +558,7 @@ static const u16* packed_or_plain_v(const torch::Tensor& q, const torch::Tensor&
     *sv = strides_qkv_slot(H, T, C);
     return (const u16*)v.data_ptr() + 2L * H * C;
   }
-  CHECK_GPU(v);
-  TORCH_CHECK(v.scalar_type() == torch::kBFloat16 && v.sizes() == q.sizes(),
-              "attn: v must be bf16 (B,H,T,C) like q, or the packed (B,T,3,H,C) qkv");
+  check_attn_bhtc(q, v, "v");
   *sv = strides_bhtc(H, T, C);
   return (const u16*)v.data_ptr();
 }
@@ -785,11 +571,8 @@ std::vector<torch::Tensor> attn_fwd_packed(torch::Tensor q, torch::Tensor k,
   int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
   auto o = torch::empty({B, T, H, C}, q.options());
   auto lse = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
-  const AttnStrides so = strides_bthc(H, T, C);
-  if (p > 0.0)
-    attn_fwd_dropout_launch(q, k, vp, sv, (u16*)o.data_ptr(), so, lse, drop_args(p, seed));
-  else
-    attn_fwd_launch(q, k, vp, sv, (u16*)o.data_ptr(), so, lse);
+  attn_fwd_launch(q, k, vp, sv, (u16*)o.data_ptr(), strides_bthc(H, T, C), lse,
+                  drop_if(p, seed));
   return {o, lse};
 }
 
@@ -806,24 +589,15 @@ std::vector<torch::Tensor> attn_bwd_packed(torch::Tensor dO, torch::Tensor q,
   check_attn_packed(q, dqkv, "dqkv");
   check_attn_bthc(q, dO, "dO");
   check_attn_bthc(q, o, "o");
-  CHECK_GPU(lse);
-  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
-  TORCH_CHECK(lse.scalar_type() == torch::kFloat && lse.numel() == (long)B * H * T,
-              "attn: lse must be fp32 (B,H,T)");
+  check_attn_lse(q, lse);
+  int H = q.size(1), T = q.size(2), C = q.size(3);
   u16* dvp = (u16*)dqkv.data_ptr() + 2L * H * C;
   const AttnStrides sdv = strides_qkv_slot(H, T, C), so = strides_bthc(H, T, C);
   torch::Tensor do_copy;
-  u16* dcp = nullptr;
-  if (stage_do) {
-    do_copy = torch::empty_like(q);
-    dcp = (u16*)do_copy.data_ptr();
-  }
-  if (p > 0.0)
-    return attn_bwd_dropout_launch((const u16*)dO.data_ptr(), so, q, k, vp, sv,
-                                   (const u16*)o.data_ptr(), so, lse, dvp, sdv,
-                                   drop_args(p, seed), dcp);
+  if (stage_do) do_copy = torch::empty_like(q);
   return attn_bwd_launch((const u16*)dO.data_ptr(), so, q, k, vp, sv,
-                         (const u16*)o.data_ptr(), so, lse, dvp, sdv, dcp);
+                         (const u16*)o.data_ptr(), so, lse, dvp, sdv, drop_if(p, seed),
+                         stage_do ? (u16*)do_copy.data_ptr() : nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -834,8 +608,7 @@ torch::Tensor embedding_bwd(torch::Tensor dy, torch::Tensor idx, long V) {
   long N = dy.size(0);
   int D = dy.size(1);
   TORCH_CHECK(D % 8 == 0, "embedding_bwd: D % 8 == 0");
-  static const bool use_atomic = getenv("MIDGPT_EMBED_ATOMIC") != nullptr;
-  if (!use_atomic && D % 64 == 0) {
+  if (D % 64 == 0) {
     // sort-based run-per-wave accumulation (exact fp32, no atomics)
     auto sorted_perm = idx.sort();
     auto sorted = std::get<0>(sorted_perm).contiguous();
@@ -874,14 +647,8 @@ torch::Tensor gelu_fwd(torch::Tensor x) {
   auto y = torch::empty_like(x);
   long n = x.numel();
   long grid = std::min((n / 8 + 255) / 256 + 1, (long)8192);
-  static const int gnt = getenv("MIDGPT_GELU_NT") ? 1 : 0;
-  if (gnt)
-    hipLaunchKernelGGL((gelu_fwd_bf16<1>), dim3(grid), dim3(256), 0, cur_stream(),
+  hipLaunchKernelGGL(gelu_fwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
                      (const u16*)x.data_ptr(), (u16*)y.data_ptr(), n);
-  else
-    hipLaunchKernelGGL((gelu_fwd_bf16<0>), dim3(grid), dim3(256), 0,
-                       cur_stream(), (const u16*)x.data_ptr(),
-                       (u16*)y.data_ptr(), n);
   launch_check();
   return y;
 }
@@ -891,15 +658,9 @@ torch::Tensor gelu_bwd(torch::Tensor dy, torch::Tensor x) {
   auto dx = torch::empty_like(x);
   long n = x.numel();
   long grid = std::min((n / 8 + 255) / 256 + 1, (long)8192);
-  static const int gnt2 = getenv("MIDGPT_GELU_NT") ? 1 : 0;
-  if (gnt2)
-    hipLaunchKernelGGL((gelu_bwd_bf16<1>), dim3(grid), dim3(256), 0, cur_stream(),
+  hipLaunchKernelGGL(gelu_bwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
                      (const u16*)dy.data_ptr(), (const u16*)x.data_ptr(),
                      (u16*)dx.data_ptr(), n);
-  else
-    hipLaunchKernelGGL((gelu_bwd_bf16<0>), dim3(grid), dim3(256), 0,
-                       cur_stream(), (const u16*)dy.data_ptr(),
-                       (const u16*)x.data_ptr(), (u16*)dx.data_ptr(), n);
   launch_check();
   return dx;
 }

@@ -47,8 +47,8 @@ __global__ void f32_to_bf16_kernel(const float* __restrict__ src,
 // Sort-based variant (default): host sorts the token ids; one WAVE per
 // run of equal tokens accumulates the permuted dY rows in fp32
 // REGISTERS and writes the bf16 dW row once — no atomics, no fp32
-// image, no conversion pass (the atomic variant above stays as the
-// MIDGPT_EMBED_ATOMIC=1 fallback). Lane l owns elements
+// image, no conversion pass (the atomic variant above serves
+// D % 64 != 0). Lane l owns elements
 // [l*c, l*c+c) of the row (c = D/64 <= 32 per pass; larger D loops).
 // ---------------------------------------------------------------------
 __global__ void embed_bwd_sorted_kernel(const u16* __restrict__ dy,

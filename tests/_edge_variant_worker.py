@@ -1,9 +1,8 @@
 """Child process of test_env_gated_variants_meet_the_default_bounds.
 
-The MIDGPT_ATTN_* / MIDGPT_EMBED_ATOMIC / MIDGPT_GELU_NT switches are read
-once into statics by the bindings, so the test starts this script afresh with
-one group of them set. It runs the attention, embedding-bwd and gelu checks of
-test_gpu_kernel_edges.py at the smallest 8-wave attention shapes and prints
+The MIDGPT_ATTN_DKV_NW4 switch is read once into a static by the bindings,
+so the test starts this script afresh with it set. It runs the attention,
+embedding-bwd and gelu checks of test_gpu_kernel_edges.py at the smallest 8-wave attention shapes and prints
 one JSON line: {"env": [switches set], "lines": [figures], "over": [figures
 over their bound]}. The bounds are those of the default path."""
 import json

@@ -129,6 +129,23 @@ def test_packed_attention_rejects_wrong_shapes():
     with pytest.raises(RuntimeError):             # dqkv not shaped like qkv
         ops._C.attn_bwd_packed(o, q, k, qkv, o, lse, randbf(B, T, 3, H, C // 2))
 
+    # the plain (B,H,T,C) entry points run the same checks
+    B, H, T, C = 1, 1, 128, 64
+    q, k, v, do = (randbf(B, H, T, C) for _ in range(4))
+    o, lse = ops._C.attn_fwd(q, k, v)
+    with pytest.raises(RuntimeError):             # k of another length
+        ops._C.attn_bwd(do, q, randbf(1, 1, 256, 64), v, o, lse)
+    with pytest.raises(RuntimeError):             # fp32 v
+        ops._C.attn_bwd(do, q, k, v.float(), o, lse)
+    with pytest.raises(RuntimeError):             # lse of the wrong length
+        ops._C.attn_bwd(do, q, k, v, o, lse[..., :-1].contiguous())
+    with pytest.raises(RuntimeError):             # k of another length
+        ops._C.attn_fwd(q, randbf(1, 1, 256, 64), v)
+    qkv, qw, kw, sin, cos = _qkv_inputs(B, T, H, C)
+    with pytest.raises(RuntimeError):             # sin one row short
+        ops._C.qkv_prep_fwd(qkv, qw, kw, sin[:T - 1].contiguous(), cos, 1e-6)
+    torch.cuda.synchronize()                      # nothing was launched: no fault to report
+
 
 # ---------------------------------------------------------------------------
 # Q/K-only prep (no T constraint; 131 rows/head: not a multiple of rows/wave)

@@ -85,28 +85,24 @@ class CausalSelfAttention(nn.Module):
     def _forward(self, x, sin, cos):
         B, T, D = x.shape
         qkv = self.c_attn(x).view(B, T, 3, self.n_head, self.head_dim)
-        ref_dropout = (self.dropout > 0.0 and self.training
-                       and os.environ.get("MIDGPT_ATTN_DROPOUT_REF") == "1")
-        if not ref_dropout and not ops.glue_unfused():
-            # Prep + attention without the transpose copies around it: O
-            # comes back as (B, T, D) and dV goes straight into dqkv.
-            o = ops.qkv_attention(qkv, self.q_ln_weight, self.k_ln_weight,
-                                  sin[:T], cos[:T],
-                                  self.dropout if self.training else 0.0)
-            return self.resid_dropout(self.c_proj(o))
-        q, k, v = ops.qkv_prep(qkv, self.q_ln_weight, self.k_ln_weight,
-                               sin[:T], cos[:T])
-        if ref_dropout:
+        if (self.dropout > 0.0 and self.training
+                and os.environ.get("MIDGPT_ATTN_DROPOUT_REF") == "1"):
             # A/B only: the materialized O(T^2) path (torch softmax +
             # F.dropout, differentiated by autograd).
             from midgpt_amd.ops import reference as refops
+            q, k, v = ops.qkv_prep(qkv, self.q_ln_weight, self.k_ln_weight,
+                                   sin[:T], cos[:T])
             o = refops.causal_attention(q, k, v, self.dropout, True)
+            o = o.transpose(1, 2).reshape(B, T, D)
         else:
+            # Prep + attention without the transpose copies around it: O
+            # comes back as (B, T, D) and dV goes straight into dqkv.
             # Attention-matrix dropout (reference src/model.py:78) runs
-            # inside the flash kernels, forward and backward.
-            o = ops.flash_attention(q, k, v,
-                                    self.dropout if self.training else 0.0)
-        o = o.transpose(1, 2).reshape(B, T, D)
+            # inside the flash kernels, forward and backward. Off the GPU
+            # and under MIDGPT_GLUE_UNFUSED=1 ops composes the separate ops.
+            o = ops.qkv_attention(qkv, self.q_ln_weight, self.k_ln_weight,
+                                  sin[:T], cos[:T],
+                                  self.dropout if self.training else 0.0)
         return self.resid_dropout(self.c_proj(o))
 
 
@@ -128,10 +124,11 @@ class MLP(nn.Module):
                     and os.environ.get("MIDGPT_FUSED_MLP") == "1"):
                 return self.dropout(ops.fused_mlp(x, self.c_fc.weight,
                                                   self.c_proj.weight))
-            # torch's gelu kernels win IN-STEP (the hand-written pair ties
-            # them in isolation, but its nontemporal stores defeat the
-            # L2 handoff to the next GEMM — rocprof: 136 vs 109 ms/4
-            # steps at xl). MIDGPT_GELU_HIP=1 opts into the native pair.
+            # torch's gelu kernels are the default. The hand-written pair
+            # ties them in isolation (NOTES_ROUND2.md, "GELU kernels");
+            # its nontemporal variant lost 25% in-step and is retired, and
+            # the plain pair has no in-step measurement of its own.
+            # MIDGPT_GELU_HIP=1 opts into the native pair.
             if os.environ.get("MIDGPT_GELU_HIP") == "1":
                 return self.dropout(self.c_proj(ops.gelu(self.c_fc(x))))
             return self.dropout(

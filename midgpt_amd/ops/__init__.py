@@ -1,5 +1,5 @@
-"""Op dispatch: hand-written HIP/CDNA4 kernels on GPU, fp32 PyTorch
-reference implementations on CPU.
+"""Op dispatch and autograd plumbing: hand-written HIP/CDNA4 kernels on GPU,
+the same interface in fp32 PyTorch (``ops/ref_backend.py``) on CPU.
 
 The HIP extension is built IN-TREE as ``midgpt_amd/ops/_C*.so`` (see
 ``setup.py`` / ``__graft_entry__.build``). On a GPU box the
@@ -9,15 +9,24 @@ to explicitly run the reference path on GPU (debugging only).
 """
 from __future__ import annotations
 
-import math
 import os
 
 import torch
 
-from midgpt_amd.ops import reference as ref
+from midgpt_amd.ops import ref_backend
 
 _C = None
 _C_ERR: str | None = None
+
+# The entry points that the extension and ref_backend both implement, with
+# the same positional arguments and the same results (count, shapes, dtypes).
+# Every op below that has a torch fallback is one call through _backend().
+BACKEND_API = (
+    "rmsnorm_fwd", "rmsnorm_bwd", "qkv_prep_fwd", "qkv_prep_bwd",
+    "attn_fwd", "attn_bwd", "attn_fwd_dropout", "attn_bwd_dropout",
+    "gelu_fwd", "gelu_bwd", "embedding_bwd", "ce_fwd", "ce_bwd",
+    "adamw_step", "kv_append", "attn_decode",
+)
 
 
 def _try_load_ext():
@@ -56,6 +65,12 @@ def _use_hip(*tensors) -> bool:
     return True
 
 
+def _backend(*tensors):
+    """The implementation of BACKEND_API for these tensors: the extension
+    where ``_use_hip`` says so, ref_backend otherwise."""
+    return _C if _use_hip(*tensors) else ref_backend
+
+
 # ----------------------------------------------------------------------------
 # RMSNorm (reference src/layers.py:60-75; plan K5)
 # ----------------------------------------------------------------------------
@@ -64,15 +79,7 @@ class _RMSNorm(torch.autograd.Function):
     def forward(ctx, x, weight, eps):
         shp = x.shape
         x2d = x.reshape(-1, shp[-1])
-        if _use_hip(x):
-            y, invrms = _C.rmsnorm_fwd(x2d.contiguous(), weight, eps)
-        else:
-            xf = x2d.float()
-            invrms = torch.rsqrt(xf.pow(2).mean(dim=-1) + eps)
-            y = xf * invrms[:, None]
-            if weight is not None:
-                y = y * weight.float()
-            y = y.to(x.dtype)
+        y, invrms = _backend(x).rmsnorm_fwd(x2d.contiguous(), weight, eps)
         ctx.save_for_backward(x2d, invrms, *( [weight] if weight is not None else [] ))
         ctx.eps = eps
         ctx.has_w = weight is not None
@@ -84,20 +91,8 @@ class _RMSNorm(torch.autograd.Function):
         x2d, invrms = saved[0], saved[1]
         weight = saved[2] if ctx.has_w else None
         dy2d = dy.reshape(x2d.shape)
-        if _use_hip(x2d):
-            dx, dw = _C.rmsnorm_bwd(dy2d.contiguous(), x2d.contiguous(), weight,
-                                    invrms, ctx.eps)
-        else:
-            D = x2d.shape[-1]
-            xf = x2d.float()
-            dyf = dy2d.float()
-            g = dyf * weight.float() if weight is not None else dyf
-            # y = x * r, r = (mean(x^2)+eps)^-1/2
-            # dx = r*g - x * r^3 * mean(x*g)
-            r = invrms[:, None]
-            mean_xg = (xf * g).mean(dim=-1, keepdim=True)
-            dx = (r * g - xf * r.pow(3) * mean_xg).to(x2d.dtype)
-            dw = (dyf * xf * r).sum(dim=0).to(weight.dtype) if weight is not None else None
+        dx, dw = _backend(x2d).rmsnorm_bwd(dy2d.contiguous(), x2d.contiguous(),
+                                           weight, invrms, ctx.eps)
         return dx.reshape(dy.shape), dw, None
 
 
@@ -164,19 +159,9 @@ def add_rmsnorm(x, r, eps: float = 1e-6):
 class _QKVPrep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, qw, kw, sin, cos, eps):
-        B, T, three, H, C = qkv.shape
-        assert three == 3
-        if _use_hip(qkv):
-            q, k, v, qstats, kstats = _C.qkv_prep_fwd(qkv.contiguous(), qw, kw,
-                                                      sin, cos, eps)
-        else:
-            qr = qkv[:, :, 0].permute(0, 2, 1, 3)  # (B,H,T,C)
-            kr = qkv[:, :, 1].permute(0, 2, 1, 3)
-            v = qkv[:, :, 2].permute(0, 2, 1, 3).contiguous()
-            qn, qstats = _ln_fwd_stats(qr, qw, eps)
-            kn, kstats = _ln_fwd_stats(kr, kw, eps)
-            q = ref.apply_rope(qn, sin, cos).contiguous()
-            k = ref.apply_rope(kn, sin, cos).contiguous()
+        assert qkv.shape[2] == 3
+        q, k, v, qstats, kstats = _backend(qkv).qkv_prep_fwd(
+            qkv.contiguous(), qw, kw, sin, cos, eps)
         ctx.save_for_backward(qkv, qw, kw, sin, cos, qstats, kstats)
         ctx.eps = eps
         return q, k, v
@@ -184,56 +169,10 @@ class _QKVPrep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dq, dk, dv):
         qkv, qw, kw, sin, cos, qstats, kstats = ctx.saved_tensors
-        if _use_hip(qkv):
-            dqkv, dqw, dkw = _C.qkv_prep_bwd(dq.contiguous(), dk.contiguous(),
-                                             dv.contiguous(), qkv.contiguous(),
-                                             qw, kw, sin, cos, qstats, kstats,
-                                             ctx.eps)
-        else:
-            # inverse RoPE rotation on dq/dk: d(rope(x)) -> cos*dy - rot(sin*dy)...
-            # rope(x) = x*cos + rot(x)*sin with rot = rotate_every_two.
-            # d/dx: dx = dy*cos + rot^T(dy*sin); rot^T = inverse rotation
-            # rot([a,b]) = [-b, a]  =>  rot^T([a,b]) = [b, -a] = -rot
-            sin2 = torch.repeat_interleave(sin, 2, dim=-1)
-            cos2 = torch.repeat_interleave(cos, 2, dim=-1)
-            dqn = (dq.float() * cos2 - ref.rotate_every_two(dq.float() * sin2))
-            dkn = (dk.float() * cos2 - ref.rotate_every_two(dk.float() * sin2))
-            qr = qkv[:, :, 0].permute(0, 2, 1, 3)
-            kr = qkv[:, :, 1].permute(0, 2, 1, 3)
-            dqr, dqw = _ln_bwd(dqn, qr, qw, qstats)
-            dkr, dkw = _ln_bwd(dkn, kr, kw, kstats)
-            dqkv = torch.empty_like(qkv)
-            dqkv[:, :, 0] = dqr.permute(0, 2, 1, 3).to(qkv.dtype)
-            dqkv[:, :, 1] = dkr.permute(0, 2, 1, 3).to(qkv.dtype)
-            dqkv[:, :, 2] = dv.permute(0, 2, 1, 3).to(qkv.dtype)
+        dqkv, dqw, dkw = _backend(qkv).qkv_prep_bwd(
+            dq.contiguous(), dk.contiguous(), dv.contiguous(), qkv.contiguous(),
+            qw, kw, sin, cos, qstats, kstats, ctx.eps)
         return dqkv, dqw, dkw, None, None, None
-
-
-def _ln_fwd_stats(x, w, eps):
-    """LayerNorm fwd returning (y, stats) with stats = (mean, invstd) fp32
-    stacked on last dim -> shape (*x.shape[:-1], 2)."""
-    xf = x.float()
-    mu = xf.mean(dim=-1, keepdim=True)
-    var = xf.var(dim=-1, unbiased=False, keepdim=True)
-    invstd = torch.rsqrt(var + eps)
-    y = ((xf - mu) * invstd * w.float()).to(x.dtype)
-    stats = torch.cat([mu, invstd], dim=-1)  # (..., 2)
-    return y, stats
-
-
-def _ln_bwd(dyf, x, w, stats):
-    """LayerNorm bwd (no bias). dyf fp32, x input tensor, stats (...,2)."""
-    xf = x.float()
-    mu = stats[..., 0:1]
-    invstd = stats[..., 1:2]
-    xhat = (xf - mu) * invstd
-    g = dyf * w.float()
-    D = xf.shape[-1]
-    mean_g = g.mean(dim=-1, keepdim=True)
-    mean_gx = (g * xhat).mean(dim=-1, keepdim=True)
-    dx = invstd * (g - mean_g - xhat * mean_gx)
-    dw = (dyf * xhat).sum(dim=tuple(range(dyf.dim() - 1))).to(w.dtype)
-    return dx, dw
 
 
 def qkv_prep(qkv, q_ln_weight, k_ln_weight, sin, cos, eps: float = 1e-6):
@@ -247,70 +186,32 @@ class _Attention(torch.autograd.Function):
     """dropout_p > 0: attention-matrix dropout with the stateless Philox
     keep-mask of csrc/philox.h, a pure function of (seed, b*H+h, q, k).
     Nothing is stored: the backward (and an activation-remat replay)
-    regenerates the mask from the seed. The CPU branch applies the bit-exact
+    regenerates the mask from the seed. ref_backend applies the bit-exact
     host mirror, so one seed gives one mask on CPU and on GPU. LSE is that of
-    the undropped softmax in both branches."""
+    the undropped softmax on both backends."""
 
     @staticmethod
     def forward(ctx, q, k, v, dropout_p=0.0, seed=0):
         ctx.dropout_p, ctx.seed = dropout_p, seed
-        if _use_hip(q):
-            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-            if dropout_p > 0.0:
-                o, lse = _C.attn_fwd_dropout(q, k, v, dropout_p, seed)
-            else:
-                o, lse = _C.attn_fwd(q, k, v)
+        impl = _backend(q)
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        if dropout_p > 0.0:
+            o, lse = impl.attn_fwd_dropout(q, k, v, dropout_p, seed)
         else:
-            B, H, T, C = q.shape
-            s = torch.matmul(q.float(), k.float().transpose(-1, -2)) / math.sqrt(C)
-            mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
-            s = s.masked_fill(~mask, float("-inf"))
-            lse = torch.logsumexp(s, dim=-1)  # (B,H,T) fp32
-            a = torch.exp(s - lse[..., None])
-            if dropout_p > 0.0:
-                a = a * _cpu_dropout_scale(seed, B, H, T, dropout_p, a)
-            o = torch.matmul(a.to(v.dtype), v)
+            o, lse = impl.attn_fwd(q, k, v)
         ctx.save_for_backward(q, k, v, o, lse)
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
-        dropout_p = ctx.dropout_p
-        if _use_hip(q):
-            if dropout_p > 0.0:
-                dq, dk, dv = _C.attn_bwd_dropout(do.contiguous(), q, k, v, o, lse,
-                                                 dropout_p, ctx.seed)
-            else:
-                dq, dk, dv = _C.attn_bwd(do.contiguous(), q, k, v, o, lse)
+        impl = _backend(q)
+        if ctx.dropout_p > 0.0:
+            dq, dk, dv = impl.attn_bwd_dropout(do.contiguous(), q, k, v, o, lse,
+                                               ctx.dropout_p, ctx.seed)
         else:
-            B, H, T, C = q.shape
-            scale = 1.0 / math.sqrt(C)
-            s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
-            mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
-            s = s.masked_fill(~mask, float("-inf"))
-            p = torch.exp(s - lse[..., None])          # undropped P (B,H,T,T) fp32
-            dof = do.float()
-            dp = torch.matmul(dof, v.float().transpose(-1, -2))
-            if dropout_p > 0.0:
-                z = _cpu_dropout_scale(ctx.seed, B, H, T, dropout_p, p)
-                dv = torch.matmul((p * z).transpose(-1, -2), dof)
-                dp = dp * z
-            else:
-                dv = torch.matmul(p.transpose(-1, -2), dof)
-            # rowsum(dO*O) = sum_j P_ij dP_ij also holds for the dropped O
-            delta = (dof * o.float()).sum(dim=-1, keepdim=True)
-            ds = p * (dp - delta)
-            dq = torch.matmul(ds, k.float()) * scale
-            dk = torch.matmul(ds.transpose(-1, -2), q.float()) * scale
-            dq, dk, dv = dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
+            dq, dk, dv = impl.attn_bwd(do.contiguous(), q, k, v, o, lse)
         return dq, dk, dv, None, None
-
-
-def _cpu_dropout_scale(seed, B, H, T, p, like):
-    """Z = keep/(1-p) from the host mirror of the kernels' keep-mask."""
-    keep = ref.attn_dropout_keep(seed, B, H, T, p)
-    return keep.to(device=like.device, dtype=like.dtype) / (1.0 - p)
 
 
 def draw_dropout_seed() -> int:
@@ -436,30 +337,8 @@ def kv_append(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
     place (nothing else) and returns q (B,H,Tn,C)."""
     pos = int(pos)
     _check_append(qkv, sin, cos, k_cache, v_cache, pos)
-    if _use_hip(qkv):
-        return _C.kv_append(qkv.contiguous(), q_ln_weight, k_ln_weight, sin, cos,
-                            k_cache, v_cache, pos, eps)
-    Tn = qkv.shape[1]
-    s, c = sin[pos:pos + Tn], cos[pos:pos + Tn]
-    q = ref.qk_layernorm(qkv[:, :, 0].permute(0, 2, 1, 3), q_ln_weight, eps)
-    k = ref.qk_layernorm(qkv[:, :, 1].permute(0, 2, 1, 3), k_ln_weight, eps)
-    k_cache[:, :, pos:pos + Tn] = ref.apply_rope(k, s, c)
-    v_cache[:, :, pos:pos + Tn] = qkv[:, :, 2].permute(0, 2, 1, 3)
-    return ref.apply_rope(q, s, c).contiguous()
-
-
-def _decode_attention_ref(q, k_cache, v_cache, kv_len):
-    """End-aligned causal attention in fp32: row i of Tq sees keys
-    [0, kv_len - Tq + i]. -> (B,Tq,H*C) in q's dtype."""
-    B, H, Tq, C = q.shape
-    k = k_cache[:, :, :kv_len].float()
-    v = v_cache[:, :, :kv_len].float()
-    s = torch.matmul(q.float(), k.transpose(-1, -2)) / math.sqrt(C)
-    qpos = torch.arange(kv_len - Tq, kv_len, device=q.device)[:, None]
-    kpos = torch.arange(kv_len, device=q.device)[None, :]
-    s = s.masked_fill(kpos > qpos, float("-inf"))
-    o = torch.matmul(torch.softmax(s, dim=-1), v).to(q.dtype)
-    return o.transpose(1, 2).reshape(B, Tq, H * C)
+    return _backend(qkv).kv_append(qkv.contiguous(), q_ln_weight, k_ln_weight,
+                                   sin, cos, k_cache, v_cache, pos, eps)
 
 
 def decode_attention(q, k_cache, v_cache, kv_len: int, num_splits: int = 0):
@@ -467,20 +346,9 @@ def decode_attention(q, k_cache, v_cache, kv_len: int, num_splits: int = 0):
     positions. Causal, end-aligned, scale 1/sqrt(C), fp32 softmax. Returns o
     (B,Tq,H*C). ``num_splits`` cuts the key range into that many slices over
     the grid (0: chosen from the sizes and the CU count; <= 64)."""
-    kv_len, num_splits = int(kv_len), int(num_splits)
     B, H, Tq, C = q.shape
-    if _use_hip(q):
-        return _C.attn_decode(q.contiguous(), k_cache, v_cache, kv_len,
-                              num_splits).view(B, Tq, H * C)
-    if kv_len > k_cache.shape[2]:
-        raise RuntimeError(f"decode_attention: kv_len {kv_len} exceeds the cache "
-                           f"({k_cache.shape[2]})")
-    if not 1 <= Tq <= min(16, kv_len):
-        raise RuntimeError("decode_attention: 1 <= Tq <= min(16, kv_len) required "
-                           f"(Tq {Tq}, kv_len {kv_len})")
-    if not 0 <= num_splits <= 64:
-        raise RuntimeError("decode_attention: num_splits must be in [0, 64]")
-    return _decode_attention_ref(q, k_cache, v_cache, kv_len)
+    return _backend(q).attn_decode(q.contiguous(), k_cache, v_cache, int(kv_len),
+                                   int(num_splits)).view(B, Tq, H * C)
 
 
 def prefill_attention(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
@@ -494,9 +362,10 @@ def prefill_attention(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
     are kept. Padding rows are harmless: LN of a zero row is finite and
     causality hides them from the real rows."""
     B, Tn, _, H, C = qkv.shape
-    if not _use_hip(qkv):
+    if _backend(qkv) is ref_backend:
+        # append, then attn_decode's math without its 16-row limit
         q = kv_append(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache, 0, eps)
-        return _decode_attention_ref(q, k_cache, v_cache, Tn)
+        return ref_backend._decode_attention_ref(q, k_cache, v_cache, Tn).view(B, Tn, H * C)
     _check_append(qkv, sin, cos, k_cache, v_cache, 0)
     Tp = -(-Tn // 128) * 128
     if Tp > k_cache.shape[2]:
@@ -521,27 +390,25 @@ def prefill_attention(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
 # ----------------------------------------------------------------------------
 # GELU (tanh approx) fwd/bwd (reference src/model.py:30; plan K7): a
 # hand-written u16x8 elementwise pair replacing the torch library kernels
-# (same numerics as F.gelu(approximate="tanh"); fp32 internal).
+# (same numerics as F.gelu(approximate="tanh"); fp32 internal). The pair is
+# bf16 with numel % 8 == 0; ref_backend takes everything else on the GPU too.
 # ----------------------------------------------------------------------------
 class _Gelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         ctx.save_for_backward(x)
-        if _use_hip(x) and x.dtype == torch.bfloat16 and x.numel() % 8 == 0:
-            return _C.gelu_fwd(x.contiguous())
-        return torch.nn.functional.gelu(x, approximate="tanh")
+        impl = _backend(x)
+        if x.dtype != torch.bfloat16 or x.numel() % 8:
+            impl = ref_backend
+        return impl.gelu_fwd(x.contiguous())
 
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        if _use_hip(x) and x.dtype == torch.bfloat16 and x.numel() % 8 == 0:
-            return _C.gelu_bwd(dy.contiguous(), x.contiguous())
-        xf = x.float()
-        c0, c1 = 0.7978845608028654, 0.044715
-        inner = c0 * (xf + c1 * xf ** 3)
-        t = torch.tanh(inner)
-        dg = 0.5 * (1 + t) + 0.5 * xf * (1 - t * t) * c0 * (1 + 3 * c1 * xf ** 2)
-        return (dy.float() * dg).to(x.dtype)
+        impl = _backend(x)
+        if x.dtype != torch.bfloat16 or x.numel() % 8:
+            impl = ref_backend
+        return impl.gelu_bwd(dy.contiguous(), x.contiguous())
 
 
 def gelu(x):
@@ -551,28 +418,23 @@ def gelu(x):
 # ----------------------------------------------------------------------------
 # Embedding: gather fwd, scatter-add bwd (reference src/layers.py:13-34;
 # plan K8). The forward gather is a plain coalesced index_select (torch);
-# the backward is the hand-written HIP fp32-accurate scatter-add.
+# the backward is the hand-written HIP fp32-accurate scatter-add (bf16).
 # ----------------------------------------------------------------------------
 class _Embedding(torch.autograd.Function):
     @staticmethod
     def forward(ctx, idx, weight):
         ctx.save_for_backward(idx)
         ctx.V = weight.shape[0]
-        ctx.wdtype = weight.dtype
         return weight[idx]
 
     @staticmethod
     def backward(ctx, dy):
         (idx,) = ctx.saved_tensors
-        D = dy.shape[-1]
-        dy2d = dy.reshape(-1, D)
-        if _use_hip(dy) and dy.dtype == torch.bfloat16:
-            dw = _C.embedding_bwd(dy2d.contiguous(), idx.reshape(-1), ctx.V)
-        else:
-            dw32 = torch.zeros(ctx.V, D, dtype=torch.float32, device=dy.device)
-            dw32.index_add_(0, idx.reshape(-1), dy2d.float())
-            dw = dw32.to(ctx.wdtype)
-        return None, dw
+        dy2d = dy.reshape(-1, dy.shape[-1])
+        impl = _backend(dy)
+        if dy.dtype != torch.bfloat16:
+            impl = ref_backend
+        return None, impl.embedding_bwd(dy2d.contiguous(), idx.reshape(-1), ctx.V)
 
 
 def embedding(idx, weight):
@@ -587,30 +449,15 @@ def embedding(idx, weight):
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets):
-        N, V = logits.shape
-        if _use_hip(logits):
-            loss_sum, lse = _C.ce_fwd(logits, targets)
-            loss = loss_sum / N
-        else:
-            lf = logits.float()
-            lse = torch.logsumexp(lf, dim=-1)
-            picked = lf.gather(1, targets[:, None]).squeeze(1)
-            loss = (lse - picked).mean()
+        loss_sum, lse = _backend(logits).ce_fwd(logits, targets)
         ctx.save_for_backward(logits, targets, lse)
-        return loss
+        return loss_sum / logits.shape[0]
 
     @staticmethod
     def backward(ctx, dloss):
         logits, targets, lse = ctx.saved_tensors
-        N, V = logits.shape
-        if _use_hip(logits):
-            dlogits = _C.ce_bwd(logits, targets, lse, dloss.float().reshape(1))
-        else:
-            lf = logits.float()
-            p = torch.exp(lf - lse[:, None])
-            p.scatter_add_(1, targets[:, None],
-                           -torch.ones(N, 1, device=p.device, dtype=p.dtype))
-            dlogits = (p * (dloss.float() / N)).to(logits.dtype)
+        dlogits = _backend(logits).ce_bwd(logits, targets, lse,
+                                          dloss.float().reshape(1))
         return dlogits, None
 
 
@@ -619,11 +466,6 @@ def cross_entropy(logits, targets):
     return _CrossEntropy.apply(logits, targets)
 
 
-# ----------------------------------------------------------------------------
-# Fused AdamW step on flat buffers (plan K10/K13). Semantics match the optax
-# chain clip_by_global_norm(1.0) -> scale_by_adam -> add_decayed_weights(
-# wd/lr_peak) -> scale_by_schedule -> scale(-1)  (reference src/train.py:153-159).
-# ----------------------------------------------------------------------------
 # ----------------------------------------------------------------------------
 # hipBLASLt DGELU-fused MLP backward: the gelu backward lives in the dgrad
 # GEMM epilogue — no separate elementwise gelu-backward kernel (plan K7).
@@ -659,6 +501,11 @@ def fused_mlp(x, w1, w2):
     return y.reshape(*shp[:-1], w2.shape[0])
 
 
+# ----------------------------------------------------------------------------
+# Fused AdamW step on flat buffers (plan K10/K13). Semantics match the optax
+# chain clip_by_global_norm(1.0) -> scale_by_adam -> add_decayed_weights(
+# wd/lr_peak) -> scale_by_schedule -> scale(-1)  (reference src/train.py:153-159).
+# ----------------------------------------------------------------------------
 def adamw_step(master: torch.Tensor, grad: torch.Tensor, m: torch.Tensor,
                v: torch.Tensor, out_bf16: torch.Tensor | None,
                *, lr: float, beta1: float, beta2: float, eps: float,
@@ -670,24 +517,11 @@ def adamw_step(master: torch.Tensor, grad: torch.Tensor, m: torch.Tensor,
     The effective gradient is ``grad * grad_scale * clip`` where
     ``clip = min(1, clip_norm / (grad_scale * sqrt(sq_sum)))`` — computed
     ON DEVICE from the (already all-reduced) squared-norm scalar ``sq_sum``
-    so the step path never syncs to host.
+    so the step path never syncs to host (ref_backend does sync).
     """
-    if master.is_cuda and _use_hip(master):
-        _C.adamw_step(master, grad, m, v,
-                      out_bf16 if out_bf16 is not None
-                      else master.new_empty(0, dtype=torch.bfloat16),
-                      out_bf16 is not None, sq_sum,
-                      lr, beta1, beta2, eps, wd_over_peak_lr,
-                      grad_scale, clip_norm, step)
-        return
-    gnorm = float(sq_sum.float().sqrt()) * grad_scale
-    clip_coef = grad_scale * min(1.0, clip_norm / (gnorm + 1e-12))
-    g = grad * clip_coef
-    m.mul_(beta1).add_(g, alpha=1 - beta1)
-    v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
-    mhat = m / (1 - beta1 ** step)
-    vhat = v / (1 - beta2 ** step)
-    update = mhat / (vhat.sqrt() + eps) + wd_over_peak_lr * master
-    master.add_(update, alpha=-lr)
-    if out_bf16 is not None:
-        out_bf16.copy_(master.to(torch.bfloat16))
+    _backend(master).adamw_step(master, grad, m, v,
+                                out_bf16 if out_bf16 is not None
+                                else master.new_empty(0, dtype=torch.bfloat16),
+                                out_bf16 is not None, sq_sum,
+                                lr, beta1, beta2, eps, wd_over_peak_lr,
+                                grad_scale, clip_norm, step)

@@ -846,7 +846,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("embedding_bwd", &embedding_bwd);
   mod.def("gelu_fwd", &gelu_fwd);
   mod.def("gelu_bwd", &gelu_bwd);
-  mod.def("linear_gelu_fwd", &linear_gelu_fwd);
   mod.def("lt_probe", &lt_probe);
   mod.def("matmul_dgelu", &matmul_dgelu);
   mod.def("probe_mfma", &probe_mfma);

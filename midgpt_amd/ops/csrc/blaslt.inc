@@ -1,8 +1,9 @@
-// hipBLASLt epilogue-fused GEMMs for the MLP (plan K7: GELU lives in the
-// GEMM epilogue, not a separate elementwise pass).
-//   linear_gelu_fwd : y = gelu_tanh(x @ w^T), aux h = pre-activation
+// hipBLASLt epilogue-fused GEMM for the MLP backward (plan K7: the GELU
+// backward lives in the GEMM epilogue, not a separate elementwise pass).
 //   matmul_dgelu    : dh = dgelu(dy @ w2, aux=h)   (the dgrad GEMM of the
 //                     second linear fused with the GELU backward)
+// The forward counterpart (GELU_AUX) has no gfx950 algorithm on ROCm 7.2;
+// lt_probe below is how that was found.
 // Row-major torch tensors are fed to hipBLASLt as their column-major
 // transposes (C_rm(M,N) == C_cm(N,M)).
 #include <hipblaslt/hipblaslt.h>
@@ -110,25 +111,6 @@ static void lt_matmul(int64_t m, int64_t n, int64_t k,
 }
 
 }  // namespace blaslt
-
-// y(M,N) = gelu(x(M,K) @ w(N,K)^T); returns {y, h} with h = pre-gelu.
-std::vector<torch::Tensor> linear_gelu_fwd(torch::Tensor x, torch::Tensor w) {
-  CHECK_GPU(x); CHECK_GPU(w);
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
-              w.scalar_type() == torch::kBFloat16);
-  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(w.size(1) == K);
-  auto y = torch::empty({M, N}, x.options());
-  auto h = torch::empty({M, N}, x.options());
-  auto ws = torch::empty({(long)blaslt::WORKSPACE},
-                         x.options().dtype(torch::kUInt8));
-  // col-major: Y_cm(N,M) = W_cm(K,N)^T x X_cm(K,M)
-  blaslt::lt_matmul(N, M, K, w.data_ptr(), HIPBLAS_OP_T, K,
-                    x.data_ptr(), HIPBLAS_OP_N, K, y.data_ptr(), N,
-                    HIPBLASLT_EPILOGUE_GELU_AUX, h.data_ptr(), N,
-                    ws.data_ptr(), cur_stream());
-  return {y, h};
-}
 
 // dh(M,N) = dgelu(dy(M,N2) @ w2(N2,N), aux = h(M,N))
 torch::Tensor matmul_dgelu(torch::Tensor dy, torch::Tensor w2, torch::Tensor h) {

@@ -1,6 +1,7 @@
 // MFMA fragment-layout helpers for v_mfma_f32_32x32x16_bf16 (gfx950).
 //
-// Layouts (verified on hardware by the mfma_probe test, tests/test_gpu_mfma.py):
+// Layouts (verified on hardware by tests/test_gpu_kernels.py::
+// test_mfma_layout_probe and ::test_mfma_pack_probe):
 //   D/C: lane l, reg r  ->  row = (r&3) + 8*(r>>2) + 4*(l>>5), col = l&31
 //   A  : lane l, j      ->  A[row = l&31][k = 8*(l>>5) + j],  j = 0..7
 //   B  : lane l, j      ->  B[k = 8*(l>>5) + j][col = l&31]

@@ -1,5 +1,6 @@
 // MFMA layout probes: verify on hardware the fragment-layout assumptions in
-// mfma.h (tests/test_gpu_mfma.py). Asymmetric inputs catch transposes
+// mfma.h (tests/test_gpu_kernels.py::test_mfma_layout_probe and
+// ::test_mfma_pack_probe). Asymmetric inputs catch transposes
 // (guide section 3 "Always A=I-check with ASYMMETRIC B").
 #include "common.h"
 #include "mfma.h"

@@ -1,0 +1,245 @@
+"""The extension's interface in fp32 torch: one plain function (no autograd)
+per entry point in ``ops.BACKEND_API``, taking the same positional arguments
+as the ``_C`` binding of that name and returning as many results with the
+same shapes and dtypes. ``ops._backend`` hands out this module wherever the
+HIP extension does not run: on the CPU and under ``MIDGPT_FORCE_REF=1``.
+
+Written apart from ``ops/reference.py`` on purpose: that module is the
+oracle of the tests, this one the code under test (hand-derived backward
+passes included). Only its RoPE / LayerNorm / keep-mask helpers are shared.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from midgpt_amd.ops import reference as ref
+
+
+# RMSNorm over (N, D) rows
+def rmsnorm_fwd(x2d, weight, eps):
+    xf = x2d.float()
+    invrms = torch.rsqrt(xf.pow(2).mean(dim=-1) + eps)
+    y = xf * invrms[:, None]
+    if weight is not None:
+        y = y * weight.float()
+    return y.to(x2d.dtype), invrms
+
+
+def rmsnorm_bwd(dy2d, x2d, weight, invrms, eps):
+    xf = x2d.float()
+    dyf = dy2d.float()
+    g = dyf * weight.float() if weight is not None else dyf
+    # y = x * r, r = (mean(x^2)+eps)^-1/2
+    # dx = r*g - x * r^3 * mean(x*g)
+    r = invrms[:, None]
+    mean_xg = (xf * g).mean(dim=-1, keepdim=True)
+    dx = (r * g - xf * r.pow(3) * mean_xg).to(x2d.dtype)
+    dw = (dyf * xf * r).sum(dim=0).to(weight.dtype) if weight is not None else None
+    return dx, dw
+
+
+# QK-LayerNorm + RoPE over the packed projection (B, T, 3, H, C)
+def _ln_fwd_stats(x, w, eps):
+    """LayerNorm fwd returning (y, stats) with stats = (mean, invstd) fp32
+    stacked on last dim -> shape (*x.shape[:-1], 2)."""
+    xf = x.float()
+    mu = xf.mean(dim=-1, keepdim=True)
+    var = xf.var(dim=-1, unbiased=False, keepdim=True)
+    invstd = torch.rsqrt(var + eps)
+    y = ((xf - mu) * invstd * w.float()).to(x.dtype)
+    stats = torch.cat([mu, invstd], dim=-1)  # (..., 2)
+    return y, stats
+
+
+def _ln_bwd(dyf, x, w, stats):
+    """LayerNorm bwd (no bias). dyf fp32, x input tensor, stats (...,2)."""
+    xf = x.float()
+    mu = stats[..., 0:1]
+    invstd = stats[..., 1:2]
+    xhat = (xf - mu) * invstd
+    g = dyf * w.float()
+    mean_g = g.mean(dim=-1, keepdim=True)
+    mean_gx = (g * xhat).mean(dim=-1, keepdim=True)
+    dx = invstd * (g - mean_g - xhat * mean_gx)
+    dw = (dyf * xhat).sum(dim=tuple(range(dyf.dim() - 1))).to(w.dtype)
+    return dx, dw
+
+
+def qkv_prep_fwd(qkv, qw, kw, sin, cos, eps):
+    qr = qkv[:, :, 0].permute(0, 2, 1, 3)  # (B,H,T,C)
+    kr = qkv[:, :, 1].permute(0, 2, 1, 3)
+    v = qkv[:, :, 2].permute(0, 2, 1, 3).contiguous()
+    qn, qstats = _ln_fwd_stats(qr, qw, eps)
+    kn, kstats = _ln_fwd_stats(kr, kw, eps)
+    q = ref.apply_rope(qn, sin, cos).contiguous()
+    k = ref.apply_rope(kn, sin, cos).contiguous()
+    return q, k, v, qstats, kstats
+
+
+def qkv_prep_bwd(dq, dk, dv, qkv, qw, kw, sin, cos, qstats, kstats, eps):
+    # rope(x) = x*cos + rot(x)*sin with rot = rotate_every_two.
+    # d/dx: dx = dy*cos + rot^T(dy*sin); rot^T = inverse rotation
+    # rot([a,b]) = [-b, a]  =>  rot^T([a,b]) = [b, -a] = -rot
+    sin2 = torch.repeat_interleave(sin, 2, dim=-1)
+    cos2 = torch.repeat_interleave(cos, 2, dim=-1)
+    dqn = (dq.float() * cos2 - ref.rotate_every_two(dq.float() * sin2))
+    dkn = (dk.float() * cos2 - ref.rotate_every_two(dk.float() * sin2))
+    qr = qkv[:, :, 0].permute(0, 2, 1, 3)
+    kr = qkv[:, :, 1].permute(0, 2, 1, 3)
+    dqr, dqw = _ln_bwd(dqn, qr, qw, qstats)
+    dkr, dkw = _ln_bwd(dkn, kr, kw, kstats)
+    dqkv = torch.empty_like(qkv)
+    dqkv[:, :, 0] = dqr.permute(0, 2, 1, 3).to(qkv.dtype)
+    dqkv[:, :, 1] = dkr.permute(0, 2, 1, 3).to(qkv.dtype)
+    dqkv[:, :, 2] = dv.permute(0, 2, 1, 3).to(qkv.dtype)
+    return dqkv, dqw, dkw
+
+
+# Causal attention, (B,H,T,C) throughout. Dropout applies the bit-exact host
+# mirror of the kernels' keep-mask, so one seed gives one mask on either
+# backend. LSE is that of the undropped softmax.
+def _cpu_dropout_scale(seed, B, H, T, p, like):
+    """Z = keep/(1-p) from the host mirror of the kernels' keep-mask."""
+    keep = ref.attn_dropout_keep(seed, B, H, T, p)
+    return keep.to(device=like.device, dtype=like.dtype) / (1.0 - p)
+
+
+def attn_fwd_dropout(q, k, v, dropout_p, seed):
+    B, H, T, C = q.shape
+    s = torch.matmul(q.float(), k.float().transpose(-1, -2)) / math.sqrt(C)
+    mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
+    s = s.masked_fill(~mask, float("-inf"))
+    lse = torch.logsumexp(s, dim=-1)  # (B,H,T) fp32
+    a = torch.exp(s - lse[..., None])
+    if dropout_p > 0.0:
+        a = a * _cpu_dropout_scale(seed, B, H, T, dropout_p, a)
+    o = torch.matmul(a.to(v.dtype), v)
+    return o, lse
+
+
+def attn_bwd_dropout(do, q, k, v, o, lse, dropout_p, seed):
+    B, H, T, C = q.shape
+    scale = 1.0 / math.sqrt(C)
+    s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
+    mask = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
+    s = s.masked_fill(~mask, float("-inf"))
+    p = torch.exp(s - lse[..., None])          # undropped P (B,H,T,T) fp32
+    dof = do.float()
+    dp = torch.matmul(dof, v.float().transpose(-1, -2))
+    if dropout_p > 0.0:
+        z = _cpu_dropout_scale(seed, B, H, T, dropout_p, p)
+        dv = torch.matmul((p * z).transpose(-1, -2), dof)
+        dp = dp * z
+    else:
+        dv = torch.matmul(p.transpose(-1, -2), dof)
+    # rowsum(dO*O) = sum_j P_ij dP_ij also holds for the dropped O
+    delta = (dof * o.float()).sum(dim=-1, keepdim=True)
+    ds = p * (dp - delta)
+    dq = torch.matmul(ds, k.float()) * scale
+    dk = torch.matmul(ds.transpose(-1, -2), q.float()) * scale
+    return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
+
+
+def attn_fwd(q, k, v):
+    return attn_fwd_dropout(q, k, v, 0.0, 0)
+
+
+def attn_bwd(do, q, k, v, o, lse):
+    return attn_bwd_dropout(do, q, k, v, o, lse, 0.0, 0)
+
+
+# KV-cache decode. Caches are (B,H,Tmax,C), written in place.
+def kv_append(qkv, qw, kw, sin, cos, k_cache, v_cache, pos, eps):
+    Tn = qkv.shape[1]
+    s, c = sin[pos:pos + Tn], cos[pos:pos + Tn]
+    q = ref.qk_layernorm(qkv[:, :, 0].permute(0, 2, 1, 3), qw, eps)
+    k = ref.qk_layernorm(qkv[:, :, 1].permute(0, 2, 1, 3), kw, eps)
+    k_cache[:, :, pos:pos + Tn] = ref.apply_rope(k, s, c)
+    v_cache[:, :, pos:pos + Tn] = qkv[:, :, 2].permute(0, 2, 1, 3)
+    return ref.apply_rope(q, s, c).contiguous()
+
+
+def _decode_attention_ref(q, k_cache, v_cache, kv_len):
+    """End-aligned causal attention in fp32: row i of Tq sees keys
+    [0, kv_len - Tq + i]. Any Tq. -> (B,Tq,H,C) in q's dtype."""
+    B, H, Tq, C = q.shape
+    k = k_cache[:, :, :kv_len].float()
+    v = v_cache[:, :, :kv_len].float()
+    s = torch.matmul(q.float(), k.transpose(-1, -2)) / math.sqrt(C)
+    qpos = torch.arange(kv_len - Tq, kv_len, device=q.device)[:, None]
+    kpos = torch.arange(kv_len, device=q.device)[None, :]
+    s = s.masked_fill(kpos > qpos, float("-inf"))
+    o = torch.matmul(torch.softmax(s, dim=-1), v).to(q.dtype)
+    return o.transpose(1, 2).contiguous()
+
+
+def attn_decode(q, k_cache, v_cache, kv_len, num_splits):
+    """The binding's argument checks, then the math (num_splits only cuts
+    the kernel's grid: nothing to do with it here)."""
+    Tq = q.shape[2]
+    if kv_len > k_cache.shape[2]:
+        raise RuntimeError(f"decode_attention: kv_len {kv_len} exceeds the cache "
+                           f"({k_cache.shape[2]})")
+    if not 1 <= Tq <= min(16, kv_len):
+        raise RuntimeError("decode_attention: 1 <= Tq <= min(16, kv_len) required "
+                           f"(Tq {Tq}, kv_len {kv_len})")
+    if not 0 <= num_splits <= 64:
+        raise RuntimeError("decode_attention: num_splits must be in [0, 64]")
+    return _decode_attention_ref(q, k_cache, v_cache, kv_len)
+
+
+# GELU (tanh approximation)
+def gelu_fwd(x):
+    return torch.nn.functional.gelu(x, approximate="tanh")
+
+
+def gelu_bwd(dy, x):
+    xf = x.float()
+    c0, c1 = 0.7978845608028654, 0.044715
+    inner = c0 * (xf + c1 * xf ** 3)
+    t = torch.tanh(inner)
+    dg = 0.5 * (1 + t) + 0.5 * xf * (1 - t * t) * c0 * (1 + 3 * c1 * xf ** 2)
+    return (dy.float() * dg).to(x.dtype)
+
+
+# Embedding backward: fp32 scatter-add of dy (N, D) into (V, D)
+def embedding_bwd(dy2d, idx, V):
+    dw32 = torch.zeros(V, dy2d.shape[-1], dtype=torch.float32, device=dy2d.device)
+    dw32.index_add_(0, idx, dy2d.float())
+    return dw32.to(dy2d.dtype)
+
+
+# Cross-entropy over (N, V) logits: (sum of the row losses, lse); the
+# backward takes dloss as a (1,) tensor and divides by N itself.
+def ce_fwd(logits, targets):
+    lf = logits.float()
+    lse = torch.logsumexp(lf, dim=-1)
+    picked = lf.gather(1, targets[:, None]).squeeze(1)
+    return (lse - picked).sum(), lse
+
+
+def ce_bwd(logits, targets, lse, gscale):
+    N = logits.shape[0]
+    lf = logits.float()
+    p = torch.exp(lf - lse[:, None])
+    p.scatter_add_(1, targets[:, None],
+                   -torch.ones(N, 1, device=p.device, dtype=p.dtype))
+    return (p * (gscale / N)).to(logits.dtype)
+
+
+# AdamW on flat fp32 buffers, in place (semantics: ops.adamw_step)
+def adamw_step(master, grad, m, v, out_bf16, write_bf16, sq_sum, lr, beta1, beta2,
+               eps, wd_over_peak_lr, grad_scale, clip_norm, step):
+    gnorm = float(sq_sum.float().sqrt()) * grad_scale
+    clip_coef = grad_scale * min(1.0, clip_norm / (gnorm + 1e-12))
+    g = grad * clip_coef
+    m.mul_(beta1).add_(g, alpha=1 - beta1)
+    v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+    mhat = m / (1 - beta1 ** step)
+    vhat = v / (1 - beta2 ** step)
+    update = mhat / (vhat.sqrt() + eps) + wd_over_peak_lr * master
+    master.add_(update, alpha=-lr)
+    if write_bf16:
+        out_bf16.copy_(master.to(torch.bfloat16))

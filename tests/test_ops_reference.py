@@ -166,6 +166,21 @@ def test_adamw_step_matches_optax_chain_semantics():
         assert torch.allclose(master, master2, atol=1e-6)
 
 
+def test_backend_api_is_implemented_by_both_backends():
+    from midgpt_amd.ops import ref_backend
+    assert len(ops.BACKEND_API) == len(set(ops.BACKEND_API)) == 16
+    for name in ops.BACKEND_API:
+        assert callable(getattr(ref_backend, name, None)), name
+        if ops.have_ext():
+            assert callable(getattr(ops._C, name, None)), name
+
+
+def test_backend_of_cpu_tensors_is_ref_backend():
+    from midgpt_amd.ops import ref_backend
+    assert ops._backend(torch.zeros(2)) is ref_backend
+    assert ops._backend(torch.zeros(2), None, 1e-6) is ref_backend
+
+
 def test_gelu_reference_path_matches_torch():
     """ops.gelu CPU fallback (fwd + hand-derived bwd) vs torch autograd."""
     import torch

@@ -15,6 +15,13 @@ in one preallocated buffer and runs the step on the HIP decode kernels
 block_size % 128 == 0. Everything else (CPU, other dtypes and shapes, or
 ``MIDGPT_DECODE_REF=1``, read at call time, for A/B) runs the eager path
 below, built from the fp32 reference ops.
+
+``generate_ragged`` decodes a batch of prompts of different lengths in one
+step per token (``prefill_ragged`` + ``decode_step_ragged`` on
+``ops.kv_append_ragged`` / ``ops.decode_attention_ragged``): per-sequence
+lengths in the ``KVCache``, every sequence advancing by the same number of
+tokens per step. It has no sliding window (a sequence whose cache is full is
+finished) and does not compact the batch when sequences finish.
 """
 from __future__ import annotations
 
@@ -80,7 +87,12 @@ class KVCache:
     block_size positions: one buffer (n_layer, 2, B, H, block_size, C), with
     per-layer views ``k[l]`` / ``v[l]`` of shape (B, H, block_size, C) and the
     number of valid positions ``pos`` kept on the host. Rows >= pos hold
-    stale or uninitialised data and are never read."""
+    stale or uninitialised data and are never read.
+
+    The ragged path keeps per-sequence lengths instead of ``pos``: the host
+    list ``lens`` and its int32 device mirror ``lens_dev``, uploaded by
+    ``set_lens`` and from then on advanced on the device by the same rule as
+    on the host (``decode_step_ragged``), so no step uploads or syncs."""
 
     def __init__(self, model, batch_size: int, device=None, dtype=None):
         cfg = model.config
@@ -97,9 +109,22 @@ class KVCache:
                       blk.attn.k_ln_weight.detach().float())
                      for blk in model.blocks]
         self.pos = 0
+        self.lens = [0] * batch_size
+        self.lens_dev = torch.zeros(batch_size, dtype=torch.int32, device=device)
 
     def reset(self):
         self.pos = 0
+        self.lens = [0] * len(self.lens)
+        self.lens_dev.zero_()
+
+    def set_lens(self, lens):
+        """Per-sequence valid positions: host list and device mirror."""
+        lens = [int(n) for n in lens]
+        if len(lens) != len(self.lens) or not all(0 <= n <= self.block_size for n in lens):
+            raise RuntimeError(f"KVCache.set_lens: {len(self.lens)} lengths in "
+                               f"[0, {self.block_size}] expected, got {lens}")
+        self.lens = lens
+        self.lens_dev.copy_(torch.tensor(lens, dtype=torch.int32))
 
 
 def _attend_cached(qkv, qw, kw, sin, cos, k_cache, v_cache, pos):
@@ -209,6 +234,195 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int,
             # from position 0 (the cached positions are invalid from here on)
             logits = step(idx[:, -block:], 0)
     return idx
+
+
+def _ragged_layers(model, idx, attend):
+    """The layer loop of ``decode_step`` with attention left to
+    ``attend(li, qkv (B,Tn,3,H,C)) -> o (B,Tn,H*C)``. Returns (x, pending):
+    the residual stream before the last MLP's output is added."""
+    cfg = model.config
+    H, C = cfg.n_head, cfg.head_dim
+    B, Tn = idx.shape
+    x = F.embedding(idx, model.wte)
+    pending = None  # residual-pending form of GPT.forward
+    for li, blk in enumerate(model.blocks):
+        if pending is None:
+            h = ops.rmsnorm(x, None, 1e-6)
+        else:
+            x, h = ops.add_rmsnorm(x, pending, 1e-6)
+        qkv = blk.attn.c_attn(h).view(B, Tn, 3, H, C)
+        x, h = ops.add_rmsnorm(x, blk.attn.c_proj(attend(li, qkv)), 1e-6)
+        pending = blk.mlp(h)
+    return x, pending
+
+
+def _ragged_logits(model, x, pending):
+    """Final norm + lm_head of one row per sequence: x, pending (B,1,D)."""
+    if pending is None:  # no blocks
+        h = ops.rmsnorm(x, None, 1e-5)
+    else:
+        _, h = ops.add_rmsnorm(x, pending, 1e-5)
+    return model.lm_head(h)[:, -1]
+
+
+def _native_cache(cache: KVCache) -> bool:
+    return cache.buf.is_cuda and cache.buf.dtype == torch.bfloat16
+
+
+@torch.no_grad()
+def prefill_ragged(model, prompts, cache: KVCache) -> torch.Tensor:
+    """Start a batch of prompts of different lengths: ``prompts`` is a list of
+    1-D int64 tensors (L_b >= 1 tokens, cropped to their last block_size).
+    Right-padded with token 0 to the longest, the batch runs once from
+    position 0; attention is causal, so the padding cannot reach a sequence's
+    real tokens. Cache rows [L_b, Lmax) of sequence b then hold padding K/V:
+    never read, since ``cache.lens[b] = L_b``, and overwritten by later
+    appends. Returns each sequence's logits at its last real token (B, V)."""
+    block = cache.block_size
+    prompts = [p.reshape(-1)[-block:] for p in prompts]
+    B = len(prompts)
+    lens = [int(p.numel()) for p in prompts]
+    if B != len(cache.lens) or min(lens, default=0) < 1:
+        raise RuntimeError(f"prefill_ragged: {len(cache.lens)} non-empty prompts "
+                           f"expected, got lengths {lens}")
+    dev = model.wte.device
+    Lmax = max(lens)
+    idx = torch.zeros(B, Lmax, dtype=torch.int64)
+    for b, p in enumerate(prompts):
+        idx[b, :lens[b]] = p
+    idx = idx.to(dev)
+    sin, cos = model.rope_sin, model.rope_cos
+    cache.set_lens([0] * B)
+
+    if _native_cache(cache) or not cache.buf.is_cuda:
+        def attend(li, qkv):
+            qw, kw = cache.ln_w[li]
+            return _attend_cached(qkv, qw, kw, sin, cos, cache.k[li], cache.v[li], 0)
+    else:
+        # ref_backend on the GPU (fp32 caches): the uniform ops would pick the
+        # kernels there, so the 16-row chunks go through the ragged pair
+        def attend(li, qkv):
+            qw, kw = cache.ln_w[li]
+            outs = []
+            for s in range(0, Lmax, 16):
+                chunk = qkv[:, s:s + 16]
+                q = ops.kv_append_ragged(chunk, qw, kw, sin, cos, cache.k[li],
+                                         cache.v[li], [s] * B)
+                outs.append(ops.decode_attention_ragged(
+                    q, cache.k[li], cache.v[li], [s + chunk.shape[1]] * B))
+            return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+
+    x, pending = _ragged_layers(model, idx, attend)
+    last = torch.tensor(lens, device=dev) - 1
+    rows = torch.arange(B, device=dev)
+    x = x[rows, last][:, None]
+    if pending is not None:
+        pending = pending[rows, last][:, None]
+    cache.set_lens(lens)
+    return _ragged_logits(model, x, pending)
+
+
+@torch.no_grad()
+def decode_step_ragged(model, idx_new: torch.Tensor, cache: KVCache) -> torch.Tensor:
+    """Run idx_new (B, Tn), Tn <= 16, with sequence b at positions
+    cache.lens[b] .. cache.lens[b]+Tn-1, appending to the cache; returns the
+    last position's logits (B, V).
+
+    A sequence whose cache is full (lens[b] == block_size) is retired: its
+    position stays frozen at the last Tn rows, which it goes on rewriting, its
+    length does not advance and its logits mean nothing. That keeps the batch
+    rectangular without a host decision per step. The device mirror of the
+    lengths follows the same rule on the device: two small launches per step,
+    no upload and no sync, however many layers read it."""
+    B, Tn = idx_new.shape
+    block = cache.block_size
+    if not 1 <= Tn <= 16:
+        raise RuntimeError(f"decode_step_ragged: 1 <= Tn <= 16 required, got {Tn}")
+    if B != len(cache.lens):
+        raise RuntimeError(f"decode_step_ragged: batch {B}, cache {len(cache.lens)}")
+    for n in cache.lens:
+        if n < block and n + Tn > block:
+            raise RuntimeError(f"decode_step_ragged: positions [{n}, {n + Tn}) "
+                               f"exceed block_size {block}")
+    pos = [min(n, block - Tn) for n in cache.lens]
+    kv_lens = [p + Tn for p in pos]
+    pos_dev = cache.lens_dev.clamp(max=block - Tn)
+    kv_lens_dev = pos_dev + Tn
+    sin, cos = model.rope_sin, model.rope_cos
+
+    def attend(li, qkv):
+        qw, kw = cache.ln_w[li]
+        q = ops.kv_append_ragged(qkv, qw, kw, sin, cos, cache.k[li], cache.v[li],
+                                 pos, pos_dev)
+        return ops.decode_attention_ragged(q, cache.k[li], cache.v[li], kv_lens,
+                                           kv_lens_dev)
+
+    x, pending = _ragged_layers(model, idx_new, attend)
+    cache.lens = kv_lens
+    cache.lens_dev = kv_lens_dev
+    return _ragged_logits(model, x[:, -1:],
+                          None if pending is None else pending[:, -1:])
+
+
+@torch.no_grad()
+def generate_ragged(model, prompts, max_new_tokens: int, temperature: float = 1.0,
+                    top_k: int | None = None, eos_id: int | None = None,
+                    generator: torch.Generator | None = None,
+                    stop_check_every: int = 16) -> list:
+    """Decode a batch of prompts of different lengths together: ``prompts`` is
+    a list of 1-D int64 tensors; returns, per prompt, the prompt plus what it
+    generated, cut after its first ``eos_id`` if that is set.
+
+    Limits. Every sequence takes one token per step. There is no sliding
+    window: a prompt is cropped to its last block_size tokens, and a sequence
+    emits at most min(max_new_tokens, block_size - L_b + 1) tokens (the last
+    one is sampled and never fed), after which it is finished. The batch is
+    not compacted: a finished sequence goes on stepping (retired, see
+    ``decode_step_ragged``) until the loop ends, and its surplus tokens are
+    dropped from the result. The loop ends when the longest budget is spent
+    or, with ``eos_id``, when a check of the device-side done-mask (one sync
+    every ``stop_check_every`` steps; a parameter, not a measured optimum)
+    finds every sequence done.
+
+    Native under ``native_decode(model)``; otherwise the same code runs on
+    ``ops.ref_backend`` with fp32 caches."""
+    model.eval()
+    block = model.config.block_size
+    dev = model.wte.device
+    prompts = [p.reshape(-1) for p in prompts]
+    B = len(prompts)
+    if B == 0:
+        return []
+    cache = KVCache(model, B, dtype=None if native_decode(model) else torch.float32)
+    lens = [min(int(p.numel()), block) for p in prompts]
+    budget = [max(0, min(int(max_new_tokens), block - n + 1)) for n in lens]
+    n_steps = max(budget)
+    if n_steps == 0:
+        return [p.clone() for p in prompts]
+    logits = prefill_ragged(model, prompts, cache)
+    toks = torch.zeros(B, n_steps, dtype=torch.int64, device=dev)
+    budget_dev = torch.tensor(budget, device=dev)
+    done = torch.zeros(B, dtype=torch.bool, device=dev)
+    for t in range(n_steps):
+        nxt = _sample(logits, temperature, top_k, generator)
+        toks[:, t] = nxt
+        if t + 1 == n_steps:
+            break
+        if eos_id is not None:
+            done |= (nxt == eos_id) | (budget_dev <= t + 1)
+            if (t + 1) % stop_check_every == 0 and bool(done.all()):
+                break
+        logits = decode_step_ragged(model, nxt[:, None], cache)
+    toks = toks.cpu()
+    out = []
+    for b, p in enumerate(prompts):
+        new = toks[b, :budget[b]]
+        if eos_id is not None:
+            hit = (new == eos_id).nonzero()
+            if hit.numel():
+                new = new[:int(hit[0]) + 1]
+        out.append(torch.cat([p, new.to(p.device)]))
+    return out
 
 
 def _sample(logits, temperature, top_k, generator):

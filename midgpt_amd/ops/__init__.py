@@ -27,6 +27,9 @@ BACKEND_API = (
     "gelu_fwd", "gelu_bwd", "embedding_bwd", "ce_fwd", "ce_bwd",
     "adamw_step", "kv_append", "attn_decode",
 )
+# The ragged decode pair (per-sequence positions / lengths), implemented by
+# both backends under the same rule as BACKEND_API.
+RAGGED_API = ("kv_append_ragged", "attn_decode_ragged")
 
 
 def _try_load_ext():
@@ -349,6 +352,64 @@ def decode_attention(q, k_cache, v_cache, kv_len: int, num_splits: int = 0):
     B, H, Tq, C = q.shape
     return _backend(q).attn_decode(q.contiguous(), k_cache, v_cache, int(kv_len),
                                    int(num_splits)).view(B, Tq, H * C)
+
+
+# Ragged decode: sequence b of the batch at its own position / length. The
+# host values (``pos`` / ``kv_lens``: Python ints or a CPU integer tensor) are
+# the truth and are validated; the kernels read an int32 GPU copy, which a
+# caller may pass (``*_dev``) to upload once per step instead of once per
+# layer and must then keep equal to the host values. fp32 caches select
+# ref_backend on any device: that is how the eager A/B path of
+# ``generate_ragged`` (MIDGPT_DECODE_REF=1) asks for it. bf16 caches on the
+# GPU run the kernels, and what they do not take raises.
+def _host_lens(vals, B, who):
+    t = vals if isinstance(vals, torch.Tensor) else torch.tensor(list(vals))
+    if t.is_cuda or t.dim() != 1 or t.shape[0] != B or t.dtype.is_floating_point \
+            or t.dtype == torch.bool:
+        raise RuntimeError(f"{who}: expected {B} integer positions on the host, "
+                           f"got {tuple(t.shape)} {t.dtype} on {t.device}")
+    return t.to(torch.int64)
+
+
+def _ragged_backend(qkv, k_cache):
+    return ref_backend if k_cache.dtype == torch.float32 else _backend(qkv)
+
+
+def _dev_lens(host, dev, like):
+    if dev is None and like.is_cuda:
+        dev = host.to(device=like.device, dtype=torch.int32)
+    return host if dev is None else dev
+
+
+def kv_append_ragged(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
+                     pos, pos_dev=None, eps: float = 1e-6):
+    """``kv_append`` with sequence b at positions pos[b] .. pos[b]+Tn-1 (RoPE
+    rows and cache rows); Tn is uniform. Returns q (B,H,Tn,C)."""
+    B, Tn = qkv.shape[:2]
+    pos = _host_lens(pos, B, "kv_append_ragged")
+    for p in pos.tolist():
+        _check_append(qkv, sin, cos, k_cache, v_cache, p)
+    return _ragged_backend(qkv, k_cache).kv_append_ragged(
+        qkv.contiguous(), q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
+        _dev_lens(pos, pos_dev, qkv), pos, eps)
+
+
+def decode_attention_ragged(q, k_cache, v_cache, kv_lens, kv_lens_dev=None,
+                            num_splits: int = 0):
+    """``decode_attention`` with sequence b holding kv_lens[b] positions: row
+    i of Tq sees keys [0, kv_lens[b] - Tq + i] of sequence b. Returns o
+    (B,Tq,H*C). ``num_splits`` = 0 applies the uniform rule to the longest
+    sequence; every row cuts its own range into that many slices."""
+    B, H, Tq, C = q.shape
+    kv_lens = _host_lens(kv_lens, B, "decode_attention_ragged")
+    Tmax = k_cache.shape[2]
+    for n in kv_lens.tolist():
+        if n > Tmax or not 1 <= Tq <= min(16, n):
+            raise RuntimeError(f"decode_attention_ragged: Tq {Tq} <= kv_len {n} <= "
+                               f"{Tmax} (the cache) required, Tq <= 16")
+    return _ragged_backend(q, k_cache).attn_decode_ragged(
+        q.contiguous(), k_cache, v_cache, _dev_lens(kv_lens, kv_lens_dev, q),
+        kv_lens, int(num_splits)).view(B, Tq, H * C)
 
 
 def prefill_attention(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,

@@ -678,12 +678,34 @@ static void check_decode_cache(const torch::Tensor& k_cache, const torch::Tensor
   TORCH_CHECK(C == 64 || C == 128, who, ": head dim 64 or 128 (got ", C, ")");
 }
 
+// Host copy of per-sequence positions or lengths: (B,) integers on the CPU.
+static std::vector<int64_t> host_lens(const torch::Tensor& t, int B, const char* who) {
+  TORCH_CHECK(!t.is_cuda() && t.dim() == 1 && t.size(0) == B &&
+              at::isIntegralType(t.scalar_type(), false),
+              who, ": the host copy must be a CPU integer tensor of ", B, " values");
+  auto t64 = t.to(torch::kLong).contiguous();
+  const int64_t* p = t64.data_ptr<int64_t>();
+  return std::vector<int64_t>(p, p + B);
+}
+
+// Device copy: (B,) int32 on the GPU, what the kernels read. Not compared
+// with the host copy (that would be a sync): keeping them equal is the
+// caller's contract.
+static const int* dev_lens(const torch::Tensor& t, int B, const char* who) {
+  CHECK_GPU(t);
+  TORCH_CHECK(t.scalar_type() == torch::kInt && t.dim() == 1 && t.size(0) == B,
+              who, ": the device copy must be (", B, ",) int32");
+  return t.data_ptr<int>();
+}
+
 // sin/cos are the FULL tables (rows >= pos+Tn, C/2) fp32; fp32 LN weights are
-// used in place, others converted.
-torch::Tensor kv_append(torch::Tensor qkv, torch::Tensor qw, torch::Tensor kw,
-                        torch::Tensor sin_t, torch::Tensor cos_t,
-                        torch::Tensor k_cache, torch::Tensor v_cache, int64_t pos,
-                        double eps) {
+// used in place, others converted. pos_dev == nullptr: every sequence at
+// pos[0]; otherwise sequence b at pos[b] (host) == pos_dev[b] (device).
+static torch::Tensor kv_append_impl(torch::Tensor qkv, torch::Tensor qw, torch::Tensor kw,
+                                    torch::Tensor sin_t, torch::Tensor cos_t,
+                                    torch::Tensor k_cache, torch::Tensor v_cache,
+                                    const std::vector<int64_t>& pos, const int* pos_dev,
+                                    double eps) {
   CHECK_GPU(qkv); CHECK_GPU(sin_t); CHECK_GPU(cos_t); CHECK_GPU(qw); CHECK_GPU(kw);
   TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "kv_append: qkv must be bf16");
   TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "kv_append: qkv must be (B,Tn,3,H,C)");
@@ -691,28 +713,54 @@ torch::Tensor kv_append(torch::Tensor qkv, torch::Tensor qw, torch::Tensor kw,
   check_decode_cache(k_cache, v_cache, B, H, C, "kv_append");
   const int64_t Tmax = k_cache.size(2);
   TORCH_CHECK(Tn >= 1, "kv_append: no new tokens");
-  TORCH_CHECK(pos >= 0 && pos + Tn <= Tmax, "kv_append: rows [", pos, ", ", pos + Tn,
-              ") do not fit a cache of ", Tmax, " rows");
   TORCH_CHECK(qw.numel() == C && kw.numel() == C, "kv_append: LN weights must be (C,)");
   TORCH_CHECK(sin_t.scalar_type() == torch::kFloat && cos_t.scalar_type() == torch::kFloat &&
               sin_t.dim() == 2 && sin_t.size(1) == C / 2 && cos_t.sizes() == sin_t.sizes(),
               "kv_append: sin/cos must be fp32 (rows, C/2)");
-  TORCH_CHECK(sin_t.size(0) >= pos + Tn, "kv_append: sin/cos tables have ", sin_t.size(0),
-              " rows, position ", pos + Tn - 1, " needed");
+  for (int64_t p : pos) {
+    TORCH_CHECK(p >= 0 && p + Tn <= Tmax, "kv_append: rows [", p, ", ", p + Tn,
+                ") do not fit a cache of ", Tmax, " rows");
+    TORCH_CHECK(sin_t.size(0) >= p + Tn, "kv_append: sin/cos tables have ", sin_t.size(0),
+                " rows, position ", p + Tn - 1, " needed");
+  }
   auto q = torch::empty({B, H, Tn, C}, qkv.options());
   auto qwf = qw.to(torch::kFloat);
   auto kwf = kw.to(torch::kFloat);
   const long nrows = (long)B * Tn * H * 3;
   const int rpb = 4 * (WAVE / (C / 8));  // rows per 256-thread block
   const long grid = std::min((nrows + rpb - 1) / rpb, (long)16384);
-  hipLaunchKernelGGL(kv_append_kernel, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const u16*)qkv.data_ptr(), qwf.data_ptr<float>(),
-                     kwf.data_ptr<float>(), sin_t.data_ptr<float>(),
-                     cos_t.data_ptr<float>(), (u16*)q.data_ptr(),
-                     (u16*)k_cache.data_ptr(), (u16*)v_cache.data_ptr(),
-                     B, Tn, H, C, (long)Tmax, (long)pos, (float)eps);
+#define LAUNCH_APPEND(RAGGED)                                                     \
+  hipLaunchKernelGGL(kv_append_kernel<RAGGED>, dim3(grid), dim3(256), 0,          \
+                     cur_stream(), (const u16*)qkv.data_ptr(),                    \
+                     qwf.data_ptr<float>(), kwf.data_ptr<float>(),                \
+                     sin_t.data_ptr<float>(), cos_t.data_ptr<float>(),            \
+                     (u16*)q.data_ptr(), (u16*)k_cache.data_ptr(),                \
+                     (u16*)v_cache.data_ptr(), B, Tn, H, C, (long)Tmax,           \
+                     (long)pos[0], pos_dev, (float)eps)
+  if (pos_dev) LAUNCH_APPEND(true);
+  else LAUNCH_APPEND(false);
+#undef LAUNCH_APPEND
   launch_check();
   return q;
+}
+
+torch::Tensor kv_append(torch::Tensor qkv, torch::Tensor qw, torch::Tensor kw,
+                        torch::Tensor sin_t, torch::Tensor cos_t,
+                        torch::Tensor k_cache, torch::Tensor v_cache, int64_t pos,
+                        double eps) {
+  return kv_append_impl(qkv, qw, kw, sin_t, cos_t, k_cache, v_cache, {pos}, nullptr, eps);
+}
+
+torch::Tensor kv_append_ragged(torch::Tensor qkv, torch::Tensor qw, torch::Tensor kw,
+                               torch::Tensor sin_t, torch::Tensor cos_t,
+                               torch::Tensor k_cache, torch::Tensor v_cache,
+                               torch::Tensor pos_dev, torch::Tensor pos_host, double eps) {
+  TORCH_CHECK(qkv.dim() == 5, "kv_append: qkv must be (B,Tn,3,H,C)");
+  const int B = qkv.size(0);
+  TORCH_CHECK(B >= 1, "kv_append: empty batch");
+  auto pos = host_lens(pos_host, B, "kv_append_ragged");
+  return kv_append_impl(qkv, qw, kw, sin_t, cos_t, k_cache, v_cache, pos,
+                        dev_lens(pos_dev, B, "kv_append_ragged"), eps);
 }
 
 static int decode_cu_count() {
@@ -745,26 +793,35 @@ int64_t attn_decode_auto_splits(int64_t rows, int64_t kv_len, int64_t cus) {
 }
 
 // q (B,H,Tq,C): the last Tq of kv_len positions; row i sees keys
-// [0, kv_len - Tq + i]. Returns o (B,Tq,H,C).
-torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
-                          int64_t kv_len, int64_t num_splits) {
+// [0, kv_len - Tq + i]. Returns o (B,Tq,H,C). lens_dev == nullptr: every
+// sequence has kv_lens[0] positions; otherwise sequence b has kv_lens[b]
+// (host) == lens_dev[b] (device), and num_splits = 0 applies the rule to the
+// longest.
+static torch::Tensor attn_decode_impl(torch::Tensor q, torch::Tensor k_cache,
+                                      torch::Tensor v_cache,
+                                      const std::vector<int64_t>& kv_lens,
+                                      const int* lens_dev, int64_t num_splits) {
   CHECK_GPU(q);
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn_decode: q must be bf16");
   TORCH_CHECK(q.dim() == 4, "attn_decode: q must be (B,H,Tq,C)");
   int B = q.size(0), H = q.size(1), Tq = q.size(2), C = q.size(3);
   check_decode_cache(k_cache, v_cache, B, H, C, "attn_decode");
   const int64_t Tmax = k_cache.size(2);
-  TORCH_CHECK(kv_len <= Tmax, "attn_decode: kv_len ", kv_len, " exceeds the cache (", Tmax, ")");
-  TORCH_CHECK(Tq >= 1 && Tq <= 16 && Tq <= kv_len,
-              "attn_decode: 1 <= Tq <= min(16, kv_len) required (Tq ", Tq, ", kv_len ",
-              kv_len, ")");
+  int64_t kv_max = 0;
+  for (int64_t kv_len : kv_lens) {
+    TORCH_CHECK(kv_len <= Tmax, "attn_decode: kv_len ", kv_len, " exceeds the cache (", Tmax, ")");
+    TORCH_CHECK(Tq >= 1 && Tq <= 16 && Tq <= kv_len,
+                "attn_decode: 1 <= Tq <= min(16, kv_len) required (Tq ", Tq, ", kv_len ",
+                kv_len, ")");
+    kv_max = std::max(kv_max, kv_len);
+  }
   TORCH_CHECK(num_splits >= 0 && num_splits <= DECODE_MAX_SPLITS,
               "attn_decode: num_splits must be in [0, ", DECODE_MAX_SPLITS, "]");
   const long rows = (long)B * H * Tq;
-  TORCH_CHECK(rows > 0 && rows < (1L << 31) && kv_len < (1L << 31),
+  TORCH_CHECK(rows > 0 && rows < (1L << 31) && kv_max < (1L << 31),
               "attn_decode: size out of range");
   if (num_splits == 0)
-    num_splits = attn_decode_auto_splits(rows, kv_len, decode_cu_count());
+    num_splits = attn_decode_auto_splits(rows, kv_max, decode_cu_count());
   const int S = (int)num_splits;
   auto o = torch::empty({B, Tq, H, C}, q.options());
   torch::Tensor ws_acc, ws_ml;
@@ -776,14 +833,14 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor 
     mlp = ws_ml.data_ptr<float>();
   }
   const float scale = 1.0f / std::sqrt((float)C);
-#define LAUNCH_DECODE(CC)                                                         \
-  hipLaunchKernelGGL(attn_decode_kernel<CC>, dim3(rows, S), dim3(256), 0,         \
+#define LAUNCH_DECODE(CC, RAGGED)                                                 \
+  hipLaunchKernelGGL((attn_decode_kernel<CC, RAGGED>), dim3(rows, S), dim3(256), 0, \
                      cur_stream(), (const u16*)q.data_ptr(),                      \
                      (const u16*)k_cache.data_ptr(), (const u16*)v_cache.data_ptr(), \
-                     (u16*)o.data_ptr(), accp, mlp, H, Tq, (long)Tmax, (int)kv_len, \
-                     S, scale)
-  if (C == 128) LAUNCH_DECODE(128);
-  else LAUNCH_DECODE(64);
+                     (u16*)o.data_ptr(), accp, mlp, H, Tq, (long)Tmax,            \
+                     (int)kv_lens[0], lens_dev, S, scale)
+  if (C == 128) { if (lens_dev) LAUNCH_DECODE(128, true); else LAUNCH_DECODE(128, false); }
+  else { if (lens_dev) LAUNCH_DECODE(64, true); else LAUNCH_DECODE(64, false); }
 #undef LAUNCH_DECODE
   launch_check();
   if (S > 1) {
@@ -792,6 +849,22 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor 
     launch_check();
   }
   return o;
+}
+
+torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+                          int64_t kv_len, int64_t num_splits) {
+  return attn_decode_impl(q, k_cache, v_cache, {kv_len}, nullptr, num_splits);
+}
+
+torch::Tensor attn_decode_ragged(torch::Tensor q, torch::Tensor k_cache,
+                                 torch::Tensor v_cache, torch::Tensor kv_lens_dev,
+                                 torch::Tensor kv_lens_host, int64_t num_splits) {
+  TORCH_CHECK(q.dim() == 4, "attn_decode: q must be (B,H,Tq,C)");
+  const int B = q.size(0);
+  TORCH_CHECK(B >= 1, "attn_decode: empty batch");
+  auto lens = host_lens(kv_lens_host, B, "attn_decode_ragged");
+  return attn_decode_impl(q, k_cache, v_cache, lens,
+                          dev_lens(kv_lens_dev, B, "attn_decode_ragged"), num_splits);
 }
 
 // ---------------------------------------------------------------------------
@@ -841,6 +914,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("pos"), py::arg("eps") = 1e-6);
   mod.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"),
           py::arg("v_cache"), py::arg("kv_len"), py::arg("num_splits") = 0);
+  mod.def("kv_append_ragged", &kv_append_ragged, py::arg("qkv"), py::arg("qw"),
+          py::arg("kw"), py::arg("sin"), py::arg("cos"), py::arg("k_cache"),
+          py::arg("v_cache"), py::arg("pos_dev"), py::arg("pos_host"),
+          py::arg("eps") = 1e-6);
+  mod.def("attn_decode_ragged", &attn_decode_ragged, py::arg("q"), py::arg("k_cache"),
+          py::arg("v_cache"), py::arg("kv_lens_dev"), py::arg("kv_lens_host"),
+          py::arg("num_splits") = 0);
   mod.def("attn_decode_auto_splits", &attn_decode_auto_splits, py::arg("rows"),
           py::arg("kv_len"), py::arg("cus"));
   mod.def("embedding_bwd", &embedding_bwd);

@@ -6,6 +6,12 @@
 //   attn_decode_kernel   Tq <= 16 query rows against the cache, split-KV.
 //   attn_decode_combine_kernel   merges the per-slice partials.
 //
+// The first two have a RAGGED instantiation that reads the position / length
+// of sequence b from an int32 array instead of one value for the batch: the
+// same body, so sequence b of a ragged call has the bits of the uniform call
+// on its slice. The uniform instantiations compile to the same resource
+// figures as before the flag (profiles/decode.md).
+//
 // Decode attention is a memory-bound stream over K and V with one query row
 // per head: no MFMA, no LDS staging. K/V rows go straight to VGPRs with
 // 16-byte loads, C/8 lanes per key row.
@@ -14,7 +20,9 @@
 
 // Same row sequence as qkv_prep_fwd_kernel<3> (row = ((b*Tn + t)*3 + role)*H
 // + h) and the same row body (qk_ln_rope_row, norms.hip); only the position
-// (pos + t) and the destinations differ.
+// (pos + t) and the destinations differ. RAGGED: sequence b starts at
+// pos_b[b] instead of pos (one more 4-byte load per row, nothing else).
+template <bool RAGGED>
 __global__ void kv_append_kernel(const u16* __restrict__ qkv,
                                  const float* __restrict__ qw,
                                  const float* __restrict__ kw,
@@ -23,7 +31,7 @@ __global__ void kv_append_kernel(const u16* __restrict__ qkv,
                                  u16* __restrict__ q, u16* __restrict__ k_cache,
                                  u16* __restrict__ v_cache,
                                  int B, int Tn, int H, int C, long Tmax, long pos,
-                                 float eps) {
+                                 const int* __restrict__ pos_b, float eps) {
   const int LPR = C / 8;                 // lanes per row (8 or 16)
   const int RPW = WAVE / LPR;            // rows per wave
   const int sub = lane_id() % LPR;
@@ -38,6 +46,12 @@ __global__ void kv_append_kernel(const u16* __restrict__ qkv,
     const long bt = rest / 3;            // = b*Tn + t
     const long t = bt % Tn;
     const long b = bt / Tn;
+    if constexpr (RAGGED) {
+      pos = pos_b[b];
+      // the binding validated the host copy; a device copy that disagrees
+      // must not write outside the cache
+      if (pos < 0 || pos + Tn > Tmax) continue;
+    }
     const u16x8 raw = *(const u16x8*)(qkv + ((bt * 3 + role) * H + h) * C + sub * 8);
     const long cache_off = ((b * H + h) * Tmax + pos + t) * C + sub * 8;
     if (role == 2) {
@@ -69,7 +83,9 @@ DEVINL float decode_weight(float m, float m_ref) {
 // sees keys [0, limit) with limit = kv_len - Tq + i + 1; the slice is
 // [k0, k1) = the split-th of num_splits equal parts of that range, possibly
 // empty. No cache row >= limit is ever loaded (the cache tail is
-// uninitialised memory).
+// uninitialised memory). RAGGED: kv_len is read per sequence from
+// kv_lens[b]; a short sequence next to a long one has short, possibly empty,
+// slices, and everything else is the same code.
 //
 // 256 threads form G = 256/(C/8) lane groups; group g takes keys k0+g,
 // k0+g+G, ... in batches of U keys whose K and V loads (2*U 16-byte loads per
@@ -78,12 +94,13 @@ DEVINL float decode_weight(float m, float m_ref) {
 // and its own 8 columns of acc. Groups merge by shuffles, waves through LDS.
 // num_splits == 1: writes o (B,Tq,H,C) bf16. Otherwise writes the slice's
 // fp32 (m, l) to ws_ml[row][split][2] and acc to ws_acc[row][split][C].
-template <int C>
+template <int C, bool RAGGED>
 __global__ __launch_bounds__(256) void attn_decode_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k_cache,
     const u16* __restrict__ v_cache, u16* __restrict__ o,
     float* __restrict__ ws_acc, float* __restrict__ ws_ml,
-    int H, int Tq, long Tmax, int kv_len, int num_splits, float scale) {
+    int H, int Tq, long Tmax, int kv_len, const int* __restrict__ kv_lens,
+    int num_splits, float scale) {
   constexpr int LPR = C / 8;
   constexpr int G = 256 / LPR;
   constexpr int U = 4;
@@ -92,6 +109,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   const int split = blockIdx.y;
   const int i = row % Tq;
   const int bh = row / Tq;
+  // min: a device copy that disagrees with the validated host one must not
+  // read past the cache
+  if constexpr (RAGGED) kv_len = min(kv_lens[bh / H], (int)Tmax);
   const int limit = kv_len - Tq + i + 1;
   const int per = (limit + num_splits - 1) / num_splits;
   const int k0 = split * per;

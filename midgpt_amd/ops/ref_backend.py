@@ -1,5 +1,5 @@
 """The extension's interface in fp32 torch: one plain function (no autograd)
-per entry point in ``ops.BACKEND_API``, taking the same positional arguments
+per entry point in ``ops.BACKEND_API`` and ``ops.RAGGED_API``, taking the same positional arguments
 as the ``_C`` binding of that name and returning as many results with the
 same shapes and dtypes. ``ops._backend`` hands out this module wherever the
 HIP extension does not run: on the CPU and under ``MIDGPT_FORCE_REF=1``.
@@ -188,6 +188,40 @@ def attn_decode(q, k_cache, v_cache, kv_len, num_splits):
     if not 0 <= num_splits <= 64:
         raise RuntimeError("decode_attention: num_splits must be in [0, 64]")
     return _decode_attention_ref(q, k_cache, v_cache, kv_len)
+
+
+# Ragged decode (ops.RAGGED_API): sequence b at its own position / length.
+# pos_host / kv_lens_host are the (B,) CPU integer tensors the bindings
+# validate; the device copies are what the kernels read and are unused here.
+def _host_lens(t, B, who):
+    if t.is_cuda or t.dim() != 1 or t.shape[0] != B or t.dtype.is_floating_point:
+        raise RuntimeError(f"{who}: the host copy must be a CPU integer tensor "
+                           f"of {B} values")
+    return [int(x) for x in t.tolist()]
+
+
+def kv_append_ragged(qkv, qw, kw, sin, cos, k_cache, v_cache, pos_dev, pos_host, eps):
+    B, Tn = qkv.shape[:2]
+    pos = _host_lens(pos_host, B, "kv_append_ragged")
+    Tmax = k_cache.shape[2]
+    for p in pos:  # all of them before the first write, as the binding does
+        if p < 0 or p + Tn > Tmax:
+            raise RuntimeError(f"kv_append: rows [{p}, {p + Tn}) do not fit a "
+                               f"cache of {Tmax} rows")
+        if sin.shape[0] < p + Tn or cos.shape[0] < p + Tn:
+            raise RuntimeError(f"kv_append: sin/cos tables have {sin.shape[0]} rows, "
+                               f"position {p + Tn - 1} needed")
+    return torch.cat([kv_append(qkv[b:b + 1], qw, kw, sin, cos, k_cache[b:b + 1],
+                                v_cache[b:b + 1], pos[b], eps)
+                      for b in range(B)], dim=0)
+
+
+def attn_decode_ragged(q, k_cache, v_cache, kv_lens_dev, kv_lens_host, num_splits):
+    B = q.shape[0]
+    lens = _host_lens(kv_lens_host, B, "attn_decode_ragged")
+    return torch.cat([attn_decode(q[b:b + 1], k_cache[b:b + 1], v_cache[b:b + 1],
+                                  lens[b], num_splits)
+                      for b in range(B)], dim=0)
 
 
 # GELU (tanh approximation)

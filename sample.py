@@ -2,6 +2,10 @@
 ``python sample.py --ckpt_dir=RUNDIR [--start=STR] [--num_samples N]
 [--max_new_tokens M] [--temperature T]``
 
+``--start`` may be given several times, or ``--start_file`` names a file with
+one prompt per line: more than one prompt decodes as one ragged batch
+(``generate_ragged``), one sample per prompt, ``--num_samples`` ignored.
+
 Loads config.json + the latest checkpoint from the rundir, rebuilds the
 model, and generates. Improvement over the reference (which re-runs a full
 forward per new token, sample.py:68-95): an incremental KV cache decode.
@@ -15,7 +19,7 @@ import pickle
 import torch
 
 from midgpt_amd.config import ExperimentConfig
-from midgpt_amd.generate import generate
+from midgpt_amd.generate import generate, generate_ragged
 from midgpt_amd.models.gpt import GPT
 from midgpt_amd.utils import checkpoint as ckpt
 
@@ -77,7 +81,13 @@ def load_model_and_tokenizer(ckpt_dir: str, device):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--ckpt_dir", required=True)
-    p.add_argument("--start", default="\n")
+    p.add_argument("--start", action="append", default=None,
+                   help="prompt; repeat for a batch of different prompts")
+    p.add_argument("--start_file", default=None,
+                   help="file with one prompt per line")
+    p.add_argument("--top_k", type=int, default=None)
+    p.add_argument("--eos_id", type=int, default=None,
+                   help="ragged batch only: end a sample at this token id")
     p.add_argument("--num_samples", type=int, default=3)
     p.add_argument("--max_new_tokens", type=int, default=200)
     p.add_argument("--temperature", type=float, default=0.8)
@@ -91,7 +101,22 @@ def main():
     gen = torch.Generator(device="cpu")
     if args.seed is not None:
         gen.manual_seed(args.seed)
-    prompt = torch.tensor(encode(args.start), dtype=torch.int64, device=device)
+    starts = list(args.start or [])
+    if args.start_file is not None:
+        with open(args.start_file) as f:
+            starts += [line.rstrip("\n") for line in f if line.strip()]
+    if len(starts) > 1:
+        prompts = [torch.tensor(encode(s), dtype=torch.int64, device=device)
+                   for s in starts]
+        outs = generate_ragged(model, prompts, args.max_new_tokens,
+                               temperature=args.temperature, top_k=args.top_k,
+                               eos_id=args.eos_id, generator=gen)
+        for o in outs:
+            print(decode(o.tolist()))
+            print("---------------")
+        return
+    start = starts[0] if starts else "\n"
+    prompt = torch.tensor(encode(start), dtype=torch.int64, device=device)
     prompt = prompt.unsqueeze(0).expand(args.num_samples, -1)
     out = generate(model, prompt, args.max_new_tokens,
                    temperature=args.temperature, generator=gen)

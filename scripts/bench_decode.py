@@ -9,6 +9,15 @@
                     the other layers' caches evict it in the same way).
   --sweep           with kernels: every num_splits in 1,2,4,..,64 next to the
                     automatic choice (the measurements behind the split rule).
+                    Then the ragged rows: attn_decode_ragged with all lengths
+                    equal next to attn_decode at the same shape (B=8 and B=64),
+                    and skewed batches (B=8, lengths spread over 128..4096) at
+                    the automatic split count (the rule on the longest
+                    sequence) and at every column of the sweep.
+  --which ragged    openwebtext_xl architecture, random weights, 8 prompts of
+                    16..512 tokens, 128 new tokens each, greedy:
+                    generate_ragged on the batch against generate() once per
+                    prompt at B=1, alternating in this process, each warmed up.
   --which e2e       generate() on the openwebtext_xl architecture, random
                     weights, 128-token prompt + 256 new tokens, greedy: native
                     path and MIDGPT_DECODE_REF=1 alternating in this process,
@@ -89,6 +98,115 @@ def bench_kv_append(B, H=16, C=128, Tmax=1024):
     print(f"kv_append   B{B} H{H} C{C} Tn1: {statistics.median(reps)*1e6:9.1f} us "
           f"(min {min(reps)*1e6:.1f} max {max(reps)*1e6:.1f})  {nbytes/1e3:.1f} kB "
           f"moved: launch-bound, back-to-back enqueue time", flush=True)
+    pos_host = torch.full((B,), 500, dtype=torch.int64)
+    pos_dev = pos_host.to(device=DEV, dtype=torch.int32)
+    fn = lambda: ops._C.kv_append_ragged(qkv, qw, kw, sin, cos, kc, vc, pos_dev,
+                                         pos_host, 1e-6)
+    reps = [time_ring([fn], 500) for _ in range(3)]
+    print(f"kv_append_ragged B{B} H{H} C{C} Tn1: {statistics.median(reps)*1e6:6.1f} us "
+          f"(min {min(reps)*1e6:.1f} max {max(reps)*1e6:.1f})", flush=True)
+
+
+def _reps_us(fns, iters):
+    reps = [time_ring(fns, iters) * 1e6 for _ in range(3)]
+    return statistics.median(reps), min(reps), max(reps)
+
+
+def bench_ragged_equal(B, H, C, kv_len):
+    """attn_decode_ragged with all lengths equal against attn_decode, the two
+    alternating (uniform, ragged, uniform, ragged ...) over the same ring."""
+    nbytes = 2 * B * H * kv_len * C * 2
+    ring = max(1, min(32, -(-RING_BYTES // nbytes)))
+    caches = [(torch.randn(B, H, kv_len, C, device=DEV, dtype=BF),
+               torch.randn(B, H, kv_len, C, device=DEV, dtype=BF))
+              for _ in range(ring)]
+    q = torch.randn(B, H, 1, C, device=DEV, dtype=BF)
+    lens_host = torch.full((B,), kv_len, dtype=torch.int64)
+    lens_dev = lens_host.to(device=DEV, dtype=torch.int32)
+    iters = 200 if nbytes < (64 << 20) else 50
+    uni = [(lambda k=k, v=v: ops._C.attn_decode(q, k, v, kv_len, 0)) for k, v in caches]
+    rag = [(lambda k=k, v=v: ops._C.attn_decode_ragged(q, k, v, lens_dev, lens_host, 0))
+           for k, v in caches]
+    res = {"uniform": [], "ragged": []}
+    for _ in range(3):
+        res["uniform"].append(time_ring(uni, iters) * 1e6)
+        res["ragged"].append(time_ring(rag, iters) * 1e6)
+    for name, r in res.items():
+        print(f"attn_decode {name:7s} B{B} H{H} C{C} kv{kv_len} auto: "
+              f"{statistics.median(r):9.1f} us (min {min(r):.1f} max {max(r):.1f})",
+              flush=True)
+    del caches
+
+
+def bench_ragged_skewed(B, H, C, lens, sweep):
+    """A skewed batch: bytes are the keys the sequences actually hold."""
+    Tmax = max(lens)
+    nbytes = 2 * H * sum(lens) * C * 2
+    alloc = 2 * B * H * Tmax * C * 2
+    ring = max(1, min(32, -(-RING_BYTES // alloc)))
+    caches = [(torch.randn(B, H, Tmax, C, device=DEV, dtype=BF),
+               torch.randn(B, H, Tmax, C, device=DEV, dtype=BF))
+              for _ in range(ring)]
+    q = torch.randn(B, H, 1, C, device=DEV, dtype=BF)
+    lens_host = torch.tensor(lens, dtype=torch.int64)
+    lens_dev = lens_host.to(device=DEV, dtype=torch.int32)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    auto = ops._C.attn_decode_auto_splits(B * H, Tmax, cus)
+    for s in [0] + ([1, 2, 4, 8, 16, 32, 64] if sweep else []):
+        fns = [(lambda k=k, v=v: ops._C.attn_decode_ragged(q, k, v, lens_dev, lens_host, s))
+               for k, v in caches]
+        med, lo, hi = _reps_us(fns, 100)
+        tag = f"auto={auto}" if s == 0 else f"{s:4d}"
+        print(f"attn_decode ragged  B{B} H{H} C{C} lens {list(lens)} splits {tag:>7}: "
+              f"{med:9.1f} us (min {lo:.1f} max {hi:.1f})  {nbytes/1e6:8.1f} MB  "
+              f"{nbytes/(med*1e-6)/1e12:5.2f} TB/s", flush=True)
+    # the same keys as a uniform batch padded to the longest: what a caller
+    # without the ragged kernel would have to read
+    fns = [(lambda k=k, v=v: ops._C.attn_decode(q, k, v, Tmax, 0)) for k, v in caches]
+    med, lo, hi = _reps_us(fns, 100)
+    print(f"attn_decode uniform B{B} H{H} C{C} all at kv{Tmax} auto={auto}: "
+          f"{med:9.1f} us (min {lo:.1f} max {hi:.1f})", flush=True)
+    del caches
+
+
+def bench_ragged_e2e(reps, n_new=128):
+    from midgpt_amd.generate import generate, generate_ragged
+    model, cfg = xl_model()
+    lens = [16, 48, 96, 160, 240, 320, 416, 512]
+    g = torch.Generator().manual_seed(0)
+    prompts = [torch.randint(0, cfg.vocab_size, (n,), generator=g).to(DEV) for n in lens]
+    print(f"ragged e2e: openwebtext_xl, prompts {lens}, {n_new} new tokens each, greedy; "
+          "time includes the prompts", flush=True)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def batch(n):
+        outs = generate_ragged(model, prompts, n, temperature=0.0)
+        assert [o.numel() for o in outs] == [m + n for m in lens]
+
+    def one_by_one(n):
+        for p in prompts:
+            assert generate(model, p[None], n, temperature=0.0).shape == (1, p.numel() + n)
+
+    for fn in (batch, one_by_one):                        # warm up both
+        fn(8)
+    res = {"generate_ragged B=8": [], "generate x8 at B=1": []}
+    for _ in range(reps):                                 # alternating
+        res["generate_ragged B=8"].append(timed(lambda: batch(n_new)))
+        res["generate x8 at B=1"].append(timed(lambda: one_by_one(n_new)))
+    for name, ts in res.items():
+        tps = sorted(len(lens) * n_new / t for t in ts)
+        print(f"ragged e2e {name:20s}: tokens/s median {statistics.median(tps):8.1f} "
+              f"min {tps[0]:8.1f} max {tps[-1]:8.1f}  (wall median "
+              f"{statistics.median(ts)*1e3:8.1f} ms) over {reps} runs", flush=True)
+    a, b = (statistics.median(res[k]) for k in res)
+    print(f"ragged e2e speed ratio of medians (batch over one-by-one): {b/a:.2f}x",
+          flush=True)
 
 
 def xl_model():
@@ -155,7 +273,7 @@ def run_count(n_new):
 
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
-    p.add_argument("--which", default="all", choices=["all", "kernels", "e2e", "count"])
+    p.add_argument("--which", default="all", choices=["all", "kernels", "ragged", "e2e", "count"])
     p.add_argument("--sweep", action="store_true")
     p.add_argument("--reps", type=int, default=3)
     p.add_argument("--new", type=int, default=32)
@@ -168,6 +286,15 @@ if __name__ == "__main__":
             bench_attn_decode(B, 32, 128, 4096, args.sweep)   # 7B shape
         for B in (1, 8, 64):
             bench_kv_append(B)
+        for B in (8, 64):
+            for kv in (128, 1024):
+                bench_ragged_equal(B, 16, 128, kv)
+            bench_ragged_equal(B, 32, 128, 4096)
+        skew = [128, 256, 512, 768, 1024, 2048, 3072, 4096]
+        bench_ragged_skewed(8, 16, 128, skew, args.sweep)
+        bench_ragged_skewed(8, 32, 128, skew, args.sweep)
+    if args.which in ("all", "ragged"):
+        bench_ragged_e2e(max(3, args.reps))
     if args.which in ("all", "e2e"):
         bench_e2e(max(3, args.reps))
     if args.which == "count":

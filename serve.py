@@ -10,6 +10,12 @@ same way sample.py does, then serves batched KV-cache generation
 
     POST /generate {"prompt": "...", "max_new_tokens": 200,
                     "temperature": 0.8, "num_samples": 1}
+    POST /generate_batch {"prompts": ["...", "..."], "max_new_tokens": 200,
+                          "temperature": 0.8, "top_k": null, "seed": null,
+                          "eos_id": null}
+         different prompts decoded together (generate_ragged): one sample per
+         prompt, each at most block_size tokens long with its prompt (no
+         sliding window), cut after its first eos_id if that is given
     GET  /healthz
 """
 import argparse
@@ -34,6 +40,14 @@ def build_app(ckpt_dir: str, device: str | None = None):
         num_samples: int = 1
         seed: int | None = None
 
+    class BatchRequest(BaseModel):
+        prompts: list[str]
+        max_new_tokens: int = 200
+        temperature: float = 0.8
+        top_k: int | None = None
+        seed: int | None = None
+        eos_id: int | None = None
+
     app = FastAPI(title="midgpt_amd")
 
     @app.get("/healthz")
@@ -54,6 +68,22 @@ def build_app(ckpt_dir: str, device: str | None = None):
                        temperature=req.temperature, generator=gen)
         return {"samples": [decode(out[i].tolist())
                             for i in range(req.num_samples)]}
+
+    @app.post("/generate_batch")
+    def generate_batch_ep(req: BatchRequest):
+        from fastapi import HTTPException
+        from midgpt_amd.generate import generate_ragged
+        prompts = [torch.tensor(encode(p), dtype=torch.long, device=device)
+                   for p in req.prompts]
+        if any(p.numel() == 0 for p in prompts):
+            raise HTTPException(status_code=422, detail="empty prompt")
+        gen = None
+        if req.seed is not None:
+            gen = torch.Generator().manual_seed(req.seed)
+        outs = generate_ragged(model, prompts, req.max_new_tokens,
+                               temperature=req.temperature, top_k=req.top_k,
+                               eos_id=req.eos_id, generator=gen)
+        return {"samples": [decode(o.tolist()) for o in outs]}
 
     return app
 

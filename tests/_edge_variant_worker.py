@@ -2,9 +2,16 @@
 
 The MIDGPT_ATTN_DKV_NW4 switch is read once into a static by the bindings,
 so the test starts this script afresh with it set. It runs the attention,
-embedding-bwd and gelu checks of test_gpu_kernel_edges.py at the smallest 8-wave attention shapes and prints
-one JSON line: {"env": [switches set], "lines": [figures], "over": [figures
-over their bound]}. The bounds are those of the default path."""
+embedding-bwd and gelu checks of test_gpu_kernel_edges.py and prints one JSON
+line: {"env": [switches set], "lines": [figures], "over": [figures over their
+bound]}. The bounds are those of the default path.
+
+What the attention part covers: T=512, C=64 and 128, no dropout, one seed.
+With the switch set the backward is attn_bwd_dkv_kernel<C,4,false> and
+attn_bwd_dq_kernel<C,4,1,false> at a T where the default path takes 8 waves;
+the forward stays the default 8-wave one. The 8-wave backward, the dropout
+kernels and every exact property of the default path are checked in the main
+process (test_attention_rows and the *_exact / *_at_8_waves tests), not here."""
 import json
 import os
 import sys

@@ -299,6 +299,71 @@ def attn_figures(q, k, v, do, got, keep=None, p=0.0, names=None):
     return figs
 
 
+SOFTMAX_PATHS = ("first", "growing", "lastB", "lastA")
+
+
+def attn_softmax_path_inputs(case: str, B, H, T, C, device="cpu", seed=15):
+    """(q, k, v, do) in bf16 with keys constructed to drive one path of the
+    online softmax. Drawn on the CPU from a fixed seed, so the GPU tests and
+    the CPU emulation see the same numbers. u is a fixed unit vector.
+
+    - ``first`` / ``lastB`` / ``lastA``: q = sqrt(C) u + noise, k = noise/2,
+      and one spiked key 8 u at position 0 / T-3 / T-40. Its score is
+      8 +- 8/sqrt(C) against N(0, 1/2) for the others, so it is the maximum of
+      every row that sees it (attn_check_path asserts that) and takes 80% or
+      more of the row's weight. No larger on purpose: once P is one-hot, o is
+      a copy of one v row, dq and dk are the rounding noise of delta alone
+      (yardstick row_err > 1), and their figures check nothing.
+    - ``growing``: q = sqrt(C) u + noise/2, k_j = (16 j / T) u + noise/2: the
+      score rises by 1 per 32-key tile, under key noise of std 0.56."""
+    g = torch.Generator().manual_seed(seed + C)
+    u = torch.randn(C, generator=g)
+    u = u / u.norm()
+    rc = math.sqrt(C)
+
+    def noise(s=1.0):
+        return torch.randn(B, H, T, C, generator=g) * s
+
+    if case == "growing":
+        j = torch.arange(T, dtype=torch.float32)[:, None]
+        q = rc * u + noise(0.5)
+        k = (16.0 * j / T) * u + noise(0.5)
+    else:
+        pos = {"first": 0, "lastB": T - 3, "lastA": T - 40}[case]
+        q = rc * u + noise()
+        k = noise(0.5)
+        k[:, :, pos] = 8.0 * u
+    v, do = noise(), noise()
+    return tuple(t.to(torch.bfloat16).to(device) for t in (q, k, v, do))
+
+
+def attn_check_path(case: str, q, k) -> str:
+    """Asserts that the inputs (never the kernel) take the path they were
+    built for, from the fp32 scores; returns a line for the EDGE output."""
+    B, H, T, C = q.shape
+    s = torch.matmul(q.float(), k.float().transpose(-1, -2)) / math.sqrt(C)
+    tril = torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
+    top = float(s[tril.expand_as(s)].abs().max())
+    s = s.masked_fill(~tril, float("-inf"))
+    if case != "growing":
+        pos = {"first": 0, "lastB": T - 3, "lastA": T - 40}[case]
+        assert bool((s[..., pos:, :].argmax(-1) == pos).all()), "the spike is not every row's max"
+        return f"max |score| {top:.1f}, key {pos} is the max of rows {pos}..{T - 1}"
+    nt = T // 32
+    tm = s.reshape(B, H, T, nt, 32).amax(-1)                    # (B,H,T,tile), -inf if unseen
+    grows = tm[..., 1:] > tm.cummax(-1).values[..., :-1]        # a later tile's max is -inf: False
+    strip_grows = grows.reshape(B, H, nt, 32, nt - 1).any(3)    # the kernels decide per wave
+    seen = torch.ones(nt, nt, dtype=torch.bool, device=q.device).tril()[:, 1:]
+    assert bool(strip_grows[..., seen].all()), "a strip has a tile in which no row's max grows"
+    pa, pb = tm[..., 0::2], tm[..., 1::2]
+    both = torch.isfinite(pb)
+    b_over_a = float((pb > pa)[both].float().mean())
+    rows = float(grows[torch.isfinite(tm[..., 1:])].float().mean())
+    assert b_over_a > 0.5 and rows > 0.5
+    return (f"max |score| {top:.1f}, max grows in every tile of every strip "
+            f"({100 * rows:.0f}% of rows x tiles), B over A in {100 * b_over_a:.0f}% of pairs")
+
+
 # ---------------------------------------------------------------------------
 # embedding backward
 # ---------------------------------------------------------------------------

@@ -71,7 +71,8 @@ def _old_attention(q, k, v, do_bhtc, p):
 @pytest.mark.parametrize("packed_v,stage_do", [(False, True), (True, False)])
 @pytest.mark.parametrize("p", [0.0, 0.25])
 @pytest.mark.parametrize("C", [64, 128])
-@pytest.mark.parametrize("T", [128, 256, 384])   # NW=4 one block, NW=8, NW=4 several
+# NW=4 one block, NW=8 one block, NW=4 several, NW=8 several (q0 > 0)
+@pytest.mark.parametrize("T", [128, 256, 384, 512])
 def test_packed_attention_equals_contiguous(T, C, p, packed_v, stage_do):
     B, H = 2, 3                                   # odd H: catches b/h stride mix-ups
     torch.manual_seed(T + C)

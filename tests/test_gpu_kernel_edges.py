@@ -5,6 +5,24 @@ attention kernels with more than one q/k block, the embedding-bwd variants,
 and the environment-gated kernels. Exact properties (causality, head
 independence, pass-through, untouched buffers) are compared bit for bit.
 
+Attention, what is covered where (main process, default launch path):
+
+- 4 waves (T % 256 == 128): T=384 and 640 in test_attention_rows and every
+  exact test.
+- 8 waves (T % 256 == 0), per row: test_attention_rows at T=256, 512, 768
+  (o, lse, dq, dk, dv; C=64 and 128; with and without dropout) and at 1024
+  (backward, C=64); test_attention_online_softmax_paths_at_8_waves and
+  test_attention_large_scores at T=512 (no dropout).
+- 8 waves, exact: first row and forward causality, backward causality of dq,
+  head independence, zero upstream rows; all at T=512, C=64 and 128, with and
+  without dropout.
+- Kernels behind those cases: no dropout, C=128 forward is the paired-tile
+  attn_fwd2_kernel<128,8>, C=64 attn_fwd_kernel<64,8,1,false>; dropout takes
+  attn_fwd_kernel<C,8,1,true>; backward attn_bwd_dkv_kernel<C,8,DROP> and
+  attn_bwd_dq_kernel<C,8,1,DROP>.
+- The child process (_edge_variant_worker.py) swaps the undropped backward to
+  4 waves at T=512; its forward is the 8-wave one again.
+
 Every test prints ``EDGE <case> <tensor>: kernel=.. yardstick=.. bound=..``;
 the figures measured on MI355X are in profiles/kernel_edge_errors.md."""
 import json
@@ -233,13 +251,22 @@ def _attn_run(q, k, v, do, drop, fwd=True):
 
 
 ATTN_SHAPES = [(1, 3, 384, 64), (1, 3, 384, 128), (3, 5, 640, 64), (3, 11, 1024, 64)]
+# T % 256 == 0: the 8-wave kernels of the default path. 256: one workgroup per
+# head, every wave on its own diagonal. 512: two q/k blocks, unmasked rounds
+# before the diagonal, 16 q tiles in the first dkv workgroup. 768: an odd
+# block count, B=2 for the batch stride, 24 and 8 q tiles in the first and
+# last dkv workgroup.
+ATTN8_SHAPES = [(1, 3, 256, 64), (1, 3, 256, 128), (1, 3, 512, 64), (1, 3, 512, 128),
+                (2, 3, 768, 64), (2, 3, 768, 128)]
+ATTN8_EXACT = [(1, 3, 512, 64), (1, 3, 512, 128)]
 
 
 @pytest.mark.parametrize("drop", [False, True], ids=["nodrop", "p0.2"])
-@pytest.mark.parametrize("B,H,T,C", ATTN_SHAPES)
+@pytest.mark.parametrize("B,H,T,C", ATTN_SHAPES + ATTN8_SHAPES)
 def test_attention_rows(B, H, T, C, drop):
     """NW=4 with more than one q/k block and odd B*H; (3,11,1024,64) is there
-    for the delta kernel's grid-stride second trip (33792 rows)."""
+    for the delta kernel's grid-stride second trip (33792 rows). ATTN8_SHAPES:
+    all five tensors of the 8-wave kernels, both head dims, both DROP values."""
     torch.manual_seed(4)
     q, k, v, do = (randbf(B, H, T, C) for _ in range(4))
     got = _attn_run(q, k, v, do, drop)
@@ -267,7 +294,13 @@ def test_attention_dropout_mask_is_the_mirror_at_4_waves(B, H, T, C):
     assert nbad == 0
 
 
-@pytest.mark.parametrize("B,H,T,C", ATTN_SHAPES[:2])
+def _t0s(T):
+    """Perturbation starts: inside a 32-key tile and on a workgroup edge; at 8
+    waves also where sub-tile B of a 64-key pair starts, in both q-blocks."""
+    return (200, 256) if T % 256 else (200, 224, 256, 288)
+
+
+@pytest.mark.parametrize("B,H,T,C", ATTN_SHAPES[:2] + ATTN8_EXACT)
 def test_attention_first_row_and_causality_exact(B, H, T, C):
     torch.manual_seed(11)
     q, k, v = (randbf(B, H, T, C) for _ in range(3))
@@ -278,7 +311,7 @@ def test_attention_first_row_and_causality_exact(B, H, T, C):
     # fp32 accumulation of C products plus STAT_ULPS ulp on the result
     tol = C * 2.0 ** -24 * (q0 * k0).abs().sum(-1) / math.sqrt(C) + U.STAT_ULPS * U.F32_ULP * s0.abs()
     assert bool(((lse[..., 0].double() - s0).abs() <= tol).all())
-    for t0 in (200, 256):                                    # inside a tile / on its edge
+    for t0 in _t0s(T):
         q2, k2, v2 = q.clone(), k.clone(), v.clone()
         for t in (q2, k2, v2):
             t[..., t0:, :] = randbf(B, H, T - t0, C, scale=3.0)
@@ -287,12 +320,32 @@ def test_attention_first_row_and_causality_exact(B, H, T, C):
             b = _attn_run(q2, k2, v2, None, drop)
             assert torch.equal(a["o"][..., :t0, :], b["o"][..., :t0, :]), (t0, drop)
             assert torch.equal(a["lse"][..., :t0], b["lse"][..., :t0]), (t0, drop)
+            assert not torch.equal(a["o"][..., t0:, :], b["o"][..., t0:, :]), (t0, drop)
 
 
 @pytest.mark.parametrize("drop", [False, True], ids=["nodrop", "p0.2"])
-def test_attention_heads_are_independent_exact(drop):
+@pytest.mark.parametrize("B,H,T,C", ATTN_SHAPES[:2] + ATTN8_EXACT)
+def test_attention_bwd_causality_exact(B, H, T, C, drop):
+    """dq of a row depends on nothing at or after t0 > row: later rows of q,
+    k, v and dO (with o and lse of the matching forward) must leave dq on rows
+    < t0 bit-identical. Masked entries have P = 0 exactly, so dS = 0 x finite;
+    the perturbation is finite for that reason (0 x NaN would fail a correct
+    kernel). Pins the dq kernel's tile loop and mask and the delta kernel."""
+    torch.manual_seed(16)
+    q, k, v, do = (randbf(B, H, T, C) for _ in range(4))
+    a = _attn_run(q, k, v, do, drop)
+    for t0 in _t0s(T):
+        pert = [t.clone() for t in (q, k, v, do)]
+        for t in pert:
+            t[..., t0:, :] = randbf(B, H, T - t0, C, scale=3.0)
+        b = _attn_run(*pert, drop)
+        assert bool(torch.isfinite(b["dq"].float()).all()), t0
+        assert torch.equal(a["dq"][..., :t0, :], b["dq"][..., :t0, :]), t0
+        assert not torch.equal(a["dq"][..., t0:, :], b["dq"][..., t0:, :]), t0
+
+
+def _heads_are_independent(B, H, T, C, drop):
     torch.manual_seed(12)
-    B, H, T, C = 2, 3, 384, 64
     q, k, v, do = (randbf(B, H, T, C) for _ in range(4))
     a = _attn_run(q, k, v, do, drop)
     q2, k2, v2, do2 = q.clone(), k.clone(), v.clone(), do.clone()
@@ -307,10 +360,18 @@ def test_attention_heads_are_independent_exact(drop):
 
 
 @pytest.mark.parametrize("drop", [False, True], ids=["nodrop", "p0.2"])
-@pytest.mark.parametrize("t0", [200, 256])
-def test_attention_zero_upstream_rows_give_exact_zero_grads(t0, drop):
+def test_attention_heads_are_independent_exact(drop):
+    _heads_are_independent(2, 3, 384, 64, drop)
+
+
+@pytest.mark.parametrize("drop", [False, True], ids=["nodrop", "p0.2"])
+@pytest.mark.parametrize("C", [64, 128])
+def test_attention_heads_are_independent_exact_at_8_waves(C, drop):
+    _heads_are_independent(2, 3, 512, C, drop)
+
+
+def _zero_upstream_rows(B, H, T, C, t0, drop):
     torch.manual_seed(13)
-    B, H, T, C = 1, 3, 384, 64
     q, k, v, do = (randbf(B, H, T, C) for _ in range(4))
     do[..., t0:, :] = 0
     g = _attn_run(q, k, v, do, drop)
@@ -319,10 +380,24 @@ def test_attention_zero_upstream_rows_give_exact_zero_grads(t0, drop):
         assert bool((g[n][..., :t0, :] != 0).any()), n
 
 
-@pytest.mark.parametrize("B,H,T,C", ATTN_SHAPES[:2])
+@pytest.mark.parametrize("drop", [False, True], ids=["nodrop", "p0.2"])
+@pytest.mark.parametrize("t0", [200, 256])
+def test_attention_zero_upstream_rows_give_exact_zero_grads(t0, drop):
+    _zero_upstream_rows(1, 3, 384, 64, t0, drop)
+
+
+@pytest.mark.parametrize("drop", [False, True], ids=["nodrop", "p0.2"])
+@pytest.mark.parametrize("t0", [200, 224, 256])
+@pytest.mark.parametrize("B,H,T,C", ATTN8_EXACT)
+def test_attention_zero_upstream_rows_give_exact_zero_grads_at_8_waves(B, H, T, C, t0, drop):
+    _zero_upstream_rows(B, H, T, C, t0, drop)
+
+
+@pytest.mark.parametrize("B,H,T,C", ATTN_SHAPES[:2] + ATTN8_EXACT)
 def test_attention_large_scores(B, H, T, C):
     """q, k at scale 4: scores q.k/sqrt(C) have std 16 and reach about +-80,
-    the running max moving from tile to tile."""
+    the running max moving from tile to tile. At T=512 this is the large-score
+    case of the 8-wave kernels' online softmax."""
     torch.manual_seed(14)
     q, k = randbf(B, H, T, C, scale=4.0), randbf(B, H, T, C, scale=4.0)
     v, do = randbf(B, H, T, C), randbf(B, H, T, C)
@@ -332,6 +407,27 @@ def test_attention_large_scores(B, H, T, C):
     for n, t in got.items():
         assert bool(torch.isfinite(t.float()).all()), n
     U.check(f"attn big B{B} H{H} T{T} C{C}", U.attn_figures(q, k, v, do, got))
+
+
+@pytest.mark.parametrize("C", [64, 128])
+@pytest.mark.parametrize("case", U.SOFTMAX_PATHS)
+def test_attention_online_softmax_paths_at_8_waves(case, C):
+    """Constructed keys (kernel_edge_util.attn_softmax_path_inputs) for the
+    paired (C=128) and single-tile (C=64) 8-wave forward:
+    first   -- key 0 is every row's max: no tile after the first rescales;
+    growing -- the max grows in every tile and sub-tile B's exceeds A's: a
+               rescale on every round, alpha from the merged max;
+    lastB   -- spike at T-3, in sub-tile B of the last pair (the per-row
+               counterpart of test_attention_fwd_spiked_max);
+    lastA   -- spike at T-40, in sub-tile A of the last pair.
+    o and lse, and dq, dk, dv of the matching backward, per row."""
+    B, H, T = 1, 2, 512
+    q, k, v, do = U.attn_softmax_path_inputs(case, B, H, T, C, DEV)
+    print(f"EDGE attn {case} B{B} H{H} T{T} C{C}: {U.attn_check_path(case, q, k)}")
+    got = _attn_run(q, k, v, do, False)
+    for n, t in got.items():
+        assert bool(torch.isfinite(t.float()).all()), n
+    U.check(f"attn {case} B{B} H{H} T{T} C{C}", U.attn_figures(q, k, v, do, got))
 
 
 # ---------------------------------------------------------------------------

@@ -1,82 +1,183 @@
 // Python bindings for the midgpt_amd HIP kernel layer (gfx950).
 // Included at the end of ext.hip (single TU — kernel definitions visible).
+//
+// Every entry point: `Call c("name", first_tensor)` sets the device guard,
+// every kernel pointer comes from c.bf16 / c.f32 / c.i64 / c.i32 (which take
+// no tensor without a shape), and every kernel goes through launch().
 #include <torch/extension.h>
 #include <hip/hip_runtime.h>
+#include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 
+#include <climits>
 #include <type_traits>
 #include <vector>
 
-#define CHECK_GPU(x) TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be contiguous GPU tensor")
+static hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
-static hipStream_t cur_stream() {
-  return c10::hip::getCurrentHIPStream().stream();
-}
-
-static void launch_check() {
+// Launch on the current stream; an empty grid launches nothing. Dynamic LDS
+// above the 64 KiB default cap (gfx950 has 160 KiB/CU) needs the attribute
+// raised first.
+template <typename... P, typename... A>
+static void launch(void (*kernel)(P...), dim3 grid, int block, size_t smem, A... args) {
+  if (grid.x == 0 || grid.y == 0 || grid.z == 0) return;
+  if (smem > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    TORCH_CHECK(e == hipSuccess, "cannot raise dynamic LDS to ", smem, " bytes: ",
+                hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(kernel, grid, dim3(block), smem, cur_stream(), static_cast<P>(args)...);
   hipError_t e = hipGetLastError();
   TORCH_CHECK(e == hipSuccess, "HIP launch failed: ", hipGetErrorString(e));
 }
 
-// Launch on the current stream. Dynamic LDS above the 64 KiB default cap
-// (gfx950 has 160 KiB/CU) needs the attribute raised first.
-template <typename... P, typename... A>
-static void launch(void (*kernel)(P...), long grid, int block, size_t smem, A... args) {
-  if (smem > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), smem, cur_stream(),
-                     static_cast<P>(args)...);
-  launch_check();
+// f(integral constant) for a run-time flag, or for a value that is A or else B.
+template <typename F>
+static void dispatch_flag(bool on, F&& f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
 }
+template <int A, int B, typename F>
+static void dispatch_int(int v, F&& f) {
+  if (v == A) f(std::integral_constant<int, A>{});
+  else f(std::integral_constant<int, B>{});
+}
+
+// What a kernel addresses of a tensor: exact sizes (ANY: a dimension that is
+// read from the tensor itself), or with flat(n) the element count alone.
+constexpr int64_t ANY = -1;
+struct Shape {
+  at::IntArrayRef sizes;
+  int64_t numel = -1;
+  Shape(std::initializer_list<int64_t> s) : sizes(s) {}
+  Shape(at::IntArrayRef s) : sizes(s) {}
+  bool fits(const torch::Tensor& t) const {
+    if (numel >= 0) return t.numel() == numel;
+    const at::IntArrayRef ts = t.sizes();
+    if (ts.size() != sizes.size()) return false;
+    for (size_t i = 0; i < sizes.size(); ++i)
+      if (sizes[i] != ANY && sizes[i] != ts[i]) return false;
+    return true;
+  }
+};
+static Shape flat(int64_t n) {
+  Shape s((at::IntArrayRef()));
+  s.numel = n;
+  return s;
+}
+static std::ostream& operator<<(std::ostream& o, const Shape& s) {
+  return s.numel >= 0 ? o << s.numel << " elements" : o << "shape " << s.sizes << " (-1: any)";
+}
+
+// Pointer to a tensor the binding has just allocated itself.
+template <typename T>
+static T* fresh(const torch::Tensor& t) {
+  return static_cast<T*>(t.data_ptr());
+}
+
+// One call of an entry point: the device guard, set to the first tensor's
+// device before anything is allocated or launched (engaged only where that is
+// not the current device: setting and restoring the current one costs three
+// runtime calls per binding call), and the only way from a caller's tensor
+// to a kernel pointer.
+struct Call {
+  const char* who;
+  int dev;
+  c10::hip::OptionalHIPGuard guard;
+
+  static int device_of(const char* who, const torch::Tensor& first) {
+    TORCH_CHECK(first.defined() && first.is_cuda(), who, ": the first tensor must be on the GPU");
+    return first.get_device();
+  }
+  Call(const char* who, const torch::Tensor& first) : who(who), dev(device_of(who, first)) {
+    if (dev != c10::hip::current_device()) guard.set_index((c10::DeviceIndex)dev);
+  }
+
+  template <typename T, c10::ScalarType ST>
+  T* ptr(const torch::Tensor& t, const char* name, const Shape& s) const {
+    TORCH_CHECK(t.defined() && t.is_cuda() && t.get_device() == dev,
+                who, ": ", name, " must be a tensor on GPU ", dev);
+    TORCH_CHECK(t.is_contiguous() && t.scalar_type() == ST && s.fits(t),
+                who, ": ", name, " must be contiguous ", ST, " of ", s, ", got ",
+                t.scalar_type(), " ", t.sizes(), t.is_contiguous() ? "" : " (strided)");
+    return static_cast<T*>(t.data_ptr());
+  }
+  // Inputs; the _out twins are for buffers of the caller's that a kernel writes.
+  const u16* bf16(const torch::Tensor& t, const char* n, const Shape& s) const {
+    return ptr<u16, torch::kBFloat16>(t, n, s);
+  }
+  u16* bf16_out(const torch::Tensor& t, const char* n, const Shape& s) const {
+    return ptr<u16, torch::kBFloat16>(t, n, s);
+  }
+  const float* f32(const torch::Tensor& t, const char* n, const Shape& s) const {
+    return ptr<float, torch::kFloat>(t, n, s);
+  }
+  float* f32_out(const torch::Tensor& t, const char* n, const Shape& s) const {
+    return ptr<float, torch::kFloat>(t, n, s);
+  }
+  const long* i64(const torch::Tensor& t, const char* n, const Shape& s) const {
+    return ptr<long, torch::kLong>(t, n, s);
+  }
+  const int* i32(const torch::Tensor& t, const char* n, const Shape& s) const {
+    return ptr<int, torch::kInt>(t, n, s);
+  }
+  // An optional tensor that is absent is a null pointer.
+  const u16* bf16(const c10::optional<torch::Tensor>& t, const char* n, const Shape& s) const {
+    return t.has_value() ? bf16(*t, n, s) : nullptr;
+  }
+  // Size i of a tensor whose rank is already checked, as an int kernel argument.
+  int dim(const torch::Tensor& t, int i) const {
+    const int64_t n = t.sizes()[i];
+    TORCH_CHECK(n <= INT_MAX, who, ": a dimension of ", n, " does not fit int");
+    return (int)n;
+  }
+};
 
 // ---------------------------------------------------------------------------
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, c10::optional<torch::Tensor> w,
                                        double eps) {
-  CHECK_GPU(x);
+  Call c("rmsnorm_fwd", x);
+  const bool fp32 = x.scalar_type() == torch::kFloat;
+  const float* xf = fp32 ? c.f32(x, "x", {ANY, ANY}) : nullptr;
+  const u16* xb = fp32 ? nullptr : c.bf16(x, "x", {ANY, ANY});
   long N = x.size(0);
-  int D = x.size(1);
+  int D = c.dim(x, 1);
+  TORCH_CHECK(fp32 || D % 8 == 0, "rmsnorm_fwd: bf16 rows need D % 8 == 0");
   auto y = torch::empty_like(x);
   auto invrms = torch::empty({N}, x.options().dtype(torch::kFloat));
   const float* wp = nullptr;
   torch::Tensor wf;
   if (w.has_value()) {
     wf = w->to(torch::kFloat).contiguous();
-    wp = wf.data_ptr<float>();
+    wp = c.f32(wf, "w", flat(D));
   }
   int rows_per_block = 4;  // 256 threads = 4 waves
   long grid = std::min((N + rows_per_block - 1) / rows_per_block, (long)8192);
-  if (x.scalar_type() == torch::kBFloat16 && D % 8 == 0) {
-    hipLaunchKernelGGL(rmsnorm_fwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
-                       (const u16*)x.data_ptr(), wp, (u16*)y.data_ptr(),
-                       invrms.data_ptr<float>(), N, D, (float)eps);
-  } else if (x.scalar_type() == torch::kFloat) {
-    hipLaunchKernelGGL((rmsnorm_fwd_kernel<float, 1>), dim3(grid), dim3(256), 0,
-                       cur_stream(), x.data_ptr<float>(), wp, y.data_ptr<float>(),
-                       invrms.data_ptr<float>(), N, D, (float)eps);
-  } else {
-    TORCH_CHECK(false, "rmsnorm: unsupported dtype/shape");
-  }
-  launch_check();
+  if (fp32)
+    launch(rmsnorm_fwd_kernel<float, 1>, grid, 256, 0, xf, wp, fresh<float>(y),
+           fresh<float>(invrms), N, D, (float)eps);
+  else
+    launch(rmsnorm_fwd_bf16, grid, 256, 0, xb, wp, fresh<u16>(y), fresh<float>(invrms), N, D,
+           (float)eps);
   return {y, invrms};
 }
 
 std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
                                        c10::optional<torch::Tensor> w,
                                        torch::Tensor invrms, double eps) {
-  CHECK_GPU(dy); CHECK_GPU(x);
-  long N = x.size(0);
-  int D = x.size(1);
-  auto dx = torch::empty_like(x);
-  long grid = std::min((N + 3) / 4, (long)8192);
+  Call c("rmsnorm_bwd", dy);
   TORCH_CHECK(!w.has_value(), "rmsnorm_bwd: weighted path unimplemented on HIP "
                               "(the model's norms are weightless)");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && D % 8 == 0,
-              "rmsnorm_bwd: bf16 with D%8==0 required");
-  hipLaunchKernelGGL(rmsnorm_bwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const u16*)dy.data_ptr(), (const u16*)x.data_ptr(),
-                     invrms.data_ptr<float>(), (u16*)dx.data_ptr(), N, D);
-  launch_check();
+  const u16* xp = c.bf16(x, "x", {ANY, ANY});
+  long N = x.size(0);
+  int D = c.dim(x, 1);
+  TORCH_CHECK(D % 8 == 0, "rmsnorm_bwd: D % 8 == 0 required");
+  const u16* dyp = c.bf16(dy, "dy", {N, D});
+  const float* ip = c.f32(invrms, "invrms", flat(N));
+  auto dx = torch::empty_like(x);
+  long grid = std::min((N + 3) / 4, (long)8192);
+  launch(rmsnorm_bwd_bf16, grid, 256, 0, dyp, xp, ip, fresh<u16>(dx), N, D);
   return {dx, torch::Tensor()};
 }
 
@@ -91,90 +192,82 @@ static void dispatch_row_width(int D, F&& f) {
 }
 
 std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x, torch::Tensor r, double eps) {
-  CHECK_GPU(x); CHECK_GPU(r);
-  TORCH_CHECK(x.dim() == 2 && r.sizes() == x.sizes(), "add_rmsnorm: x, r must be (N, D)");
+  Call c("add_rmsnorm_fwd", x);
+  const u16* xp = c.bf16(x, "x", {ANY, ANY});
+  const u16* rp = c.bf16(r, "r", x.sizes());
   long N = x.size(0);
-  int D = x.size(1);
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
-              r.scalar_type() == torch::kBFloat16 && D % 8 == 0,
-              "add_rmsnorm: bf16 with D%8==0 required");
+  int D = c.dim(x, 1);
+  TORCH_CHECK(D % 8 == 0, "add_rmsnorm_fwd: D % 8 == 0 required");
   auto s = torch::empty_like(x);
   auto y = torch::empty_like(x);
   auto invrms = torch::empty({N}, x.options().dtype(torch::kFloat));
   long grid = std::min((N + 3) / 4, (long)8192);
-  if (N > 0)
-    dispatch_row_width(D, [&](auto w) {
-      launch(add_rmsnorm_fwd_bf16<decltype(w)::value>, grid, 256, 0,
-             (const u16*)x.data_ptr(), (const u16*)r.data_ptr(), (u16*)s.data_ptr(),
-             (u16*)y.data_ptr(), invrms.data_ptr<float>(), N, D, (float)eps);
-    });
+  dispatch_row_width(D, [&](auto w) {
+    launch(add_rmsnorm_fwd_bf16<decltype(w)::value>, grid, 256, 0, xp, rp, fresh<u16>(s),
+           fresh<u16>(y), fresh<float>(invrms), N, D, (float)eps);
+  });
   return {s, y, invrms};
 }
 
 torch::Tensor add_rmsnorm_bwd(c10::optional<torch::Tensor> ds, torch::Tensor dy,
                               torch::Tensor s, torch::Tensor invrms) {
-  CHECK_GPU(dy); CHECK_GPU(s); CHECK_GPU(invrms);
-  TORCH_CHECK(s.dim() == 2 && dy.sizes() == s.sizes(), "add_rmsnorm_bwd: dy, s must be (N, D)");
+  Call c("add_rmsnorm_bwd", dy);
+  const u16* sp = c.bf16(s, "s", {ANY, ANY});
   long N = s.size(0);
-  int D = s.size(1);
-  TORCH_CHECK(s.scalar_type() == torch::kBFloat16 &&
-              dy.scalar_type() == torch::kBFloat16 && D % 8 == 0,
-              "add_rmsnorm_bwd: bf16 with D%8==0 required");
-  TORCH_CHECK(invrms.scalar_type() == torch::kFloat && invrms.numel() == N,
-              "add_rmsnorm_bwd: invrms must be fp32 (N,)");
-  const u16* dsp = nullptr;
-  if (ds.has_value()) {
-    CHECK_GPU((*ds));
-    TORCH_CHECK(ds->scalar_type() == torch::kBFloat16 && ds->sizes() == s.sizes(),
-                "add_rmsnorm_bwd: ds must be bf16 (N, D)");
-    dsp = (const u16*)ds->data_ptr();
-  }
+  int D = c.dim(s, 1);
+  TORCH_CHECK(D % 8 == 0, "add_rmsnorm_bwd: D % 8 == 0 required");
+  const u16* dyp = c.bf16(dy, "dy", {N, D});
+  const u16* dsp = c.bf16(ds, "ds", {N, D});
+  const float* ip = c.f32(invrms, "invrms", flat(N));
   auto dx = torch::empty_like(s);
   long grid = std::min((N + 3) / 4, (long)8192);
-  if (N > 0)
-    dispatch_row_width(D, [&](auto w) {
-      launch(add_rmsnorm_bwd_bf16<decltype(w)::value>, grid, 256, 0, dsp,
-             (const u16*)dy.data_ptr(), (const u16*)s.data_ptr(),
-             invrms.data_ptr<float>(), (u16*)dx.data_ptr(), N, D);
-    });
+  dispatch_row_width(D, [&](auto w) {
+    launch(add_rmsnorm_bwd_bf16<decltype(w)::value>, grid, 256, 0, dsp, dyp, sp, ip,
+           fresh<u16>(dx), N, D);
+  });
   return dx;
 }
 
 // ---------------------------------------------------------------------------
 // What the qkv_prep kernels read besides the gradients, checked once: the
 // packed projection (B,T,3,H,C) bf16, LN weights (C,) and RoPE tables of at
-// least T rows of C/2, the latter four as contiguous fp32.
+// least T rows of C/2, the latter four converted to contiguous fp32.
 struct PrepInputs {
   int B, T, H, C;
-  torch::Tensor qw, kw, sin, cos;  // fp32
+  const u16* qkv;
+  const float *qw, *kw, *sin, *cos;
+  torch::Tensor keep[4];  // the fp32 tensors those four point into
 };
-static PrepInputs prep_inputs(const torch::Tensor& qkv, const torch::Tensor& qw,
+static PrepInputs prep_inputs(const Call& c, const torch::Tensor& qkv, const torch::Tensor& qw,
                               const torch::Tensor& kw, const torch::Tensor& sin_t,
                               const torch::Tensor& cos_t) {
-  CHECK_GPU(qkv);
-  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "qkv_prep: qkv must be bf16");
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "qkv_prep: qkv must be (B,T,3,H,C)");
-  int B = qkv.size(0), T = qkv.size(1), H = qkv.size(3), C = qkv.size(4);
+  PrepInputs in;
+  in.qkv = c.bf16(qkv, "qkv", {ANY, ANY, 3, ANY, ANY});
+  in.B = c.dim(qkv, 0), in.T = c.dim(qkv, 1), in.H = c.dim(qkv, 3), in.C = c.dim(qkv, 4);
+  const int C = in.C;
   // The kernels reduce over C/8 lanes with width-(C/8) shuffles and put
   // 64/(C/8) rows in a wave: C/8 must be a power of two that divides 64.
   TORCH_CHECK(C == 8 || C == 16 || C == 32 || C == 64 || C == 128,
-              "qkv_prep: head dim must be 8, 16, 32, 64 or 128 (got ", C, ")");
-  TORCH_CHECK(qw.is_cuda() && kw.is_cuda() && qw.numel() == C && kw.numel() == C,
-              "qkv_prep: weights must be GPU tensors of (C,)");
-  TORCH_CHECK(sin_t.is_cuda() && cos_t.is_cuda() && sin_t.dim() == 2 &&
-              sin_t.size(0) >= T && sin_t.size(1) == C / 2 &&
-              cos_t.sizes() == sin_t.sizes(),
-              "qkv_prep: sin/cos must be GPU tensors of (>= T, C/2)");
-  auto f32 = [](const torch::Tensor& t) { return t.to(torch::kFloat).contiguous(); };
-  return {B, T, H, C, f32(qw), f32(kw), f32(sin_t), f32(cos_t)};
+              c.who, ": head dim must be 8, 16, 32, 64 or 128 (got ", C, ")");
+  auto fp32 = [&](int slot, const torch::Tensor& t, const char* name, const Shape& s) {
+    in.keep[slot] = t.to(torch::kFloat).contiguous();
+    return c.f32(in.keep[slot], name, s);
+  };
+  in.qw = fp32(0, qw, "qw", flat(C));
+  in.kw = fp32(1, kw, "kw", flat(C));
+  in.sin = fp32(2, sin_t, "sin", {ANY, C / 2});
+  in.cos = fp32(3, cos_t, "cos", sin_t.sizes());
+  TORCH_CHECK(sin_t.size(0) >= in.T, c.who, ": sin/cos must have at least T rows");
+  return in;
 }
 
 // SLOTS = 3: q, k and the V copy; SLOTS = 2: q and k only (v undefined).
 template <int SLOTS>
-static std::vector<torch::Tensor> prep_fwd(torch::Tensor qkv, torch::Tensor qw,
+static std::vector<torch::Tensor> prep_fwd(const char* who, torch::Tensor qkv, torch::Tensor qw,
                                            torch::Tensor kw, torch::Tensor sin_t,
                                            torch::Tensor cos_t, double eps) {
-  const PrepInputs in = prep_inputs(qkv, qw, kw, sin_t, cos_t);
+  Call c(who, qkv);
+  const PrepInputs in = prep_inputs(c, qkv, qw, kw, sin_t, cos_t);
   const int B = in.B, T = in.T, H = in.H, C = in.C;
   auto opt = qkv.options();
   auto q = torch::empty({B, H, T, C}, opt);
@@ -185,42 +278,28 @@ static std::vector<torch::Tensor> prep_fwd(torch::Tensor qkv, torch::Tensor qw,
   auto kstats = torch::empty({B, H, T, 2}, opt.dtype(torch::kFloat));
   long nrows = (long)B * T * H * SLOTS;
   long grid = std::min((nrows + 3) / 4, (long)16384);
-  if (nrows > 0)
-    hipLaunchKernelGGL(qkv_prep_fwd_kernel<SLOTS>, dim3(grid), dim3(256), 0, cur_stream(),
-                       (const u16*)qkv.data_ptr(), in.qw.data_ptr<float>(),
-                       in.kw.data_ptr<float>(), in.sin.data_ptr<float>(),
-                       in.cos.data_ptr<float>(), (u16*)q.data_ptr(), (u16*)k.data_ptr(),
-                       SLOTS == 3 ? (u16*)v.data_ptr() : (u16*)nullptr,
-                       qstats.data_ptr<float>(), kstats.data_ptr<float>(),
-                       B, T, H, C, (float)eps);
-  launch_check();
+  launch(qkv_prep_fwd_kernel<SLOTS>, grid, 256, 0, in.qkv, in.qw, in.kw, in.sin, in.cos,
+         fresh<u16>(q), fresh<u16>(k), SLOTS == 3 ? fresh<u16>(v) : nullptr,
+         fresh<float>(qstats), fresh<float>(kstats), B, T, H, C, (float)eps);
   return {q, k, v, qstats, kstats};
 }
 
 // Fills slots 0 and 1 of dqkv, and slot 2 from dv where one is given
 // (otherwise attn_bwd_packed writes it). Returns {dqw, dkw}.
-static std::vector<torch::Tensor> prep_bwd(torch::Tensor dq, torch::Tensor dk,
-                                           const torch::Tensor* dv, torch::Tensor qkv,
-                                           torch::Tensor qw, torch::Tensor kw,
+static std::vector<torch::Tensor> prep_bwd(const Call& c, torch::Tensor dq, torch::Tensor dk,
+                                           const c10::optional<torch::Tensor>& dv,
+                                           torch::Tensor qkv, torch::Tensor qw, torch::Tensor kw,
                                            torch::Tensor sin_t, torch::Tensor cos_t,
                                            torch::Tensor qstats, torch::Tensor kstats,
                                            torch::Tensor dqkv) {
-  const PrepInputs in = prep_inputs(qkv, qw, kw, sin_t, cos_t);
+  const PrepInputs in = prep_inputs(c, qkv, qw, kw, sin_t, cos_t);
   const int B = in.B, T = in.T, H = in.H, C = in.C;
   const long n = (long)B * H * T * C;
-  for (const torch::Tensor* g : std::initializer_list<const torch::Tensor*>{&dq, &dk, dv}) {
-    if (!g) continue;
-    CHECK_GPU((*g));
-    TORCH_CHECK(g->scalar_type() == torch::kBFloat16 && g->numel() == n,
-                "qkv_prep_bwd: dq, dk, dv must be bf16 (B,H,T,C)");
-  }
-  CHECK_GPU(qstats); CHECK_GPU(kstats); CHECK_GPU(dqkv);
-  TORCH_CHECK(qstats.scalar_type() == torch::kFloat &&
-              kstats.scalar_type() == torch::kFloat &&
-              qstats.numel() == (long)B * H * T * 2 && kstats.numel() == qstats.numel(),
-              "qkv_prep_bwd: stats must be fp32 (B,H,T,2)");
-  TORCH_CHECK(dqkv.scalar_type() == torch::kBFloat16 && dqkv.sizes() == qkv.sizes(),
-              "qkv_prep_bwd: dqkv must be bf16 with qkv's shape");
+  const u16 *dqp = c.bf16(dq, "dq", flat(n)), *dkp = c.bf16(dk, "dk", flat(n));
+  const u16* dvp = c.bf16(dv, "dv", flat(n));
+  const float* qsp = c.f32(qstats, "qstats", flat(n / C * 2));
+  const float* ksp = c.f32(kstats, "kstats", flat(n / C * 2));
+  u16* dqkvp = c.bf16_out(dqkv, "dqkv", qkv.sizes());
   // One row sequence and grid with or without dv (V rows skipped without):
   // that keeps the partial sums, hence dqw and dkw, bit-identical.
   long nrows = (long)B * T * H * 3;
@@ -228,24 +307,16 @@ static std::vector<torch::Tensor> prep_bwd(torch::Tensor dq, torch::Tensor dk,
   auto dqw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
   auto dkw_p = torch::empty({nblocks, C}, qkv.options().dtype(torch::kFloat));
   size_t smem = 4 * 2 * C * sizeof(float);  // [waves = 256/64][2][C]
-  auto kernel = dv ? qkv_prep_bwd_kernel<true> : qkv_prep_bwd_kernel<false>;
-  if (nrows > 0)
-    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(256), smem, cur_stream(),
-                       (const u16*)dq.data_ptr(), (const u16*)dk.data_ptr(),
-                       dv ? (const u16*)dv->data_ptr() : (const u16*)nullptr,
-                       (const u16*)qkv.data_ptr(), in.qw.data_ptr<float>(),
-                       in.kw.data_ptr<float>(), in.sin.data_ptr<float>(),
-                       in.cos.data_ptr<float>(), qstats.data_ptr<float>(),
-                       kstats.data_ptr<float>(), (u16*)dqkv.data_ptr(),
-                       dqw_p.data_ptr<float>(), dkw_p.data_ptr<float>(), B, T, H, C);
-  launch_check();
+  auto kernel = dvp ? qkv_prep_bwd_kernel<true> : qkv_prep_bwd_kernel<false>;
+  launch(kernel, nblocks, 256, smem, dqp, dkp, dvp, in.qkv, in.qw, in.kw, in.sin, in.cos, qsp,
+         ksp, dqkvp, fresh<float>(dqw_p), fresh<float>(dkw_p), B, T, H, C);
   return {dqw_p.sum(0).to(qw.scalar_type()), dkw_p.sum(0).to(kw.scalar_type())};
 }
 
 std::vector<torch::Tensor> qkv_prep_fwd(torch::Tensor qkv, torch::Tensor qw,
                                         torch::Tensor kw, torch::Tensor sin_t,
                                         torch::Tensor cos_t, double eps) {
-  return prep_fwd<3>(qkv, qw, kw, sin_t, cos_t, eps);
+  return prep_fwd<3>("qkv_prep_fwd", qkv, qw, kw, sin_t, cos_t, eps);
 }
 
 std::vector<torch::Tensor> qkv_prep_bwd(torch::Tensor dq, torch::Tensor dk,
@@ -254,8 +325,9 @@ std::vector<torch::Tensor> qkv_prep_bwd(torch::Tensor dq, torch::Tensor dk,
                                         torch::Tensor sin_t, torch::Tensor cos_t,
                                         torch::Tensor qstats, torch::Tensor kstats,
                                         double eps) {
+  Call c("qkv_prep_bwd", dq);
   auto dqkv = torch::empty_like(qkv);
-  auto dw = prep_bwd(dq, dk, &dv, qkv, qw, kw, sin_t, cos_t, qstats, kstats, dqkv);
+  auto dw = prep_bwd(c, dq, dk, dv, qkv, qw, kw, sin_t, cos_t, qstats, kstats, dqkv);
   return {dqkv, dw[0], dw[1]};
 }
 
@@ -263,7 +335,7 @@ std::vector<torch::Tensor> qkv_prep_bwd(torch::Tensor dq, torch::Tensor dk,
 std::vector<torch::Tensor> qk_prep_fwd(torch::Tensor qkv, torch::Tensor qw,
                                        torch::Tensor kw, torch::Tensor sin_t,
                                        torch::Tensor cos_t, double eps) {
-  auto r = prep_fwd<2>(qkv, qw, kw, sin_t, cos_t, eps);
+  auto r = prep_fwd<2>("qk_prep_fwd", qkv, qw, kw, sin_t, cos_t, eps);
   return {r[0], r[1], r[3], r[4]};
 }
 
@@ -272,40 +344,41 @@ std::vector<torch::Tensor> qk_prep_bwd(torch::Tensor dq, torch::Tensor dk,
                                        torch::Tensor kw, torch::Tensor sin_t,
                                        torch::Tensor cos_t, torch::Tensor qstats,
                                        torch::Tensor kstats, torch::Tensor dqkv) {
-  return prep_bwd(dq, dk, nullptr, qkv, qw, kw, sin_t, cos_t, qstats, kstats, dqkv);
+  Call c("qk_prep_bwd", dq);
+  return prep_bwd(c, dq, dk, c10::nullopt, qkv, qw, kw, sin_t, cos_t, qstats, kstats, dqkv);
 }
 
 // ---------------------------------------------------------------------------
+// targets[i] in [0, V) is the caller's contract: checking it would be a sync.
 std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor targets) {
-  CHECK_GPU(logits); CHECK_GPU(targets);
-  TORCH_CHECK(logits.scalar_type() == torch::kBFloat16, "logits must be bf16");
+  Call c("ce_fwd", logits);
+  const u16* lp = c.bf16(logits, "logits", {ANY, ANY});
   long N = logits.size(0);
-  int V = logits.size(1);
+  int V = c.dim(logits, 1);
+  const long* tp = c.i64(targets, "targets", flat(N));
   auto lse = torch::empty({N}, logits.options().dtype(torch::kFloat));
   auto loss_sum = torch::zeros({1}, logits.options().dtype(torch::kFloat));
   long grid = std::min(N, (long)8192);
-  hipLaunchKernelGGL(ce_fwd_kernel, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const u16*)logits.data_ptr(), targets.data_ptr<long>(),
-                     lse.data_ptr<float>(), loss_sum.data_ptr<float>(), N, V);
-  launch_check();
+  launch(ce_fwd_kernel, grid, 256, 0, lp, tp, fresh<float>(lse), fresh<float>(loss_sum), N, V);
   return {loss_sum.squeeze(0), lse};
 }
 
 torch::Tensor ce_bwd(torch::Tensor logits, torch::Tensor targets, torch::Tensor lse,
                      torch::Tensor gscale) {
-  CHECK_GPU(logits);
+  Call c("ce_bwd", logits);
+  const u16* lp = c.bf16(logits, "logits", {ANY, ANY});
   long N = logits.size(0);
-  int V = logits.size(1);
-  auto dlogits = torch::empty_like(logits);
-  // gscale tensor = dloss (scalar); kernel multiplies by 1/N itself? no —
-  // host passes dloss/N as a device scalar: divide here without sync.
+  int V = c.dim(logits, 1);
+  const long* tp = c.i64(targets, "targets", flat(N));
+  const float* lsep = c.f32(lse, "lse", flat(N));
+  TORCH_CHECK(gscale.defined() && gscale.numel() == 1, "ce_bwd: gscale must hold one value");
+  // gscale = dloss, one value on the device; the kernel wants dloss / N:
+  // divide here, without a sync.
   auto gs = (gscale.to(torch::kFloat) / (double)N).contiguous();
+  const float* gsp = c.f32(gs, "gscale", flat(1));
+  auto dlogits = torch::empty_like(logits);
   long grid = std::min(N, (long)8192);
-  hipLaunchKernelGGL(ce_bwd_kernel, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const u16*)logits.data_ptr(), targets.data_ptr<long>(),
-                     lse.data_ptr<float>(), gs.data_ptr<float>(),
-                     (u16*)dlogits.data_ptr(), N, V);
-  launch_check();
+  launch(ce_bwd_kernel, grid, 256, 0, lp, tp, lsep, gsp, fresh<u16>(dlogits), N, V);
   return dlogits;
 }
 
@@ -314,19 +387,19 @@ void adamw_step(torch::Tensor master, torch::Tensor grad, torch::Tensor m,
                 torch::Tensor v, torch::Tensor out_bf16, bool write_bf16,
                 torch::Tensor sq_sum, double lr, double b1, double b2, double eps,
                 double wd, double grad_scale, double clip_norm, long step) {
-  CHECK_GPU(master);
+  Call c("adamw_step", master);
   long n = master.numel();
+  float* mp = c.f32_out(master, "master", flat(n));
+  const float* gp = c.f32(grad, "grad", flat(n));
+  float *m1 = c.f32_out(m, "m", flat(n)), *m2 = c.f32_out(v, "v", flat(n));
+  u16* op = write_bf16 ? c.bf16_out(out_bf16, "out_bf16", flat(n)) : nullptr;
+  const float* sqp = c.f32(sq_sum, "sq_sum", flat(1));
   float bc1 = 1.f / (1.f - powf((float)b1, (float)step));
   float bc2 = 1.f / (1.f - powf((float)b2, (float)step));
   long grid = std::min((n / 4 + 255) / 256 + 1, (long)4096);
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, cur_stream(),
-                     master.data_ptr<float>(), grad.data_ptr<float>(),
-                     m.data_ptr<float>(), v.data_ptr<float>(),
-                     write_bf16 ? (u16*)out_bf16.data_ptr() : nullptr,
-                     (int)write_bf16, sq_sum.data_ptr<float>(),
-                     (float)lr, (float)b1, (float)b2, (float)eps, (float)wd,
-                     (float)grad_scale, (float)clip_norm, bc1, bc2, n);
-  launch_check();
+  launch(adamw_kernel, grid, 256, 0, mp, gp, m1, m2, op, (int)write_bf16, sqp, (float)lr,
+         (float)b1, (float)b2, (float)eps, (float)wd, (float)grad_scale, (float)clip_norm, bc1,
+         bc2, n);
 }
 
 // ---------------------------------------------------------------------------
@@ -341,44 +414,21 @@ static AttnStrides strides_qkv_slot(int H, int T, int C) {  // one slot of (B,T,
   return {(long)T * 3 * H * C, (long)C, 3 * H * C};
 }
 
-// Argument checks shared by every attention entry point.
-static void check_attn_qk(const torch::Tensor& q, const torch::Tensor& k) {
-  CHECK_GPU(q); CHECK_GPU(k);
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
-              k.scalar_type() == torch::kBFloat16, "attn: bf16 required");
-  TORCH_CHECK(q.dim() == 4 && k.sizes() == q.sizes(), "attn: q, k must be (B,H,T,C)");
+// q and k (B,H,T,C) of every attention entry point, checked. Everything else
+// is held to these sizes: {B,H,T,C}, {B,T,H,C}, packed {B,T,3,H,C}, lse B*H*T.
+struct AttnQK {
+  int B, H, T, C;
+  const u16 *q, *k;
+  torch::TensorOptions opt;
+  long rows() const { return (long)B * H * T; }
+};
+static AttnQK attn_qk(const Call& c, const torch::Tensor& q, const torch::Tensor& k) {
+  const u16* qp = c.bf16(q, "q", {ANY, ANY, ANY, ANY});
+  const u16* kp = c.bf16(k, "k", q.sizes());
   TORCH_CHECK(q.size(2) % 128 == 0, "attn: T % 128 == 0 required (got ", q.size(2), ")");
   TORCH_CHECK(q.size(3) == 64 || q.size(3) == 128,
               "attn: head dim 64 or 128 (got ", q.size(3), ")");
-}
-static void check_attn_bhtc(const torch::Tensor& q, const torch::Tensor& x,
-                            const char* name) {
-  CHECK_GPU(x);
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.sizes() == q.sizes(),
-              "attn: ", name, " must be bf16 (B,H,T,C) like q");
-}
-// qkv (B,T,3,H,C) that q, k (B,H,T,C) were made from.
-static void check_attn_packed(const torch::Tensor& q, const torch::Tensor& qkv,
-                              const char* name) {
-  CHECK_GPU(qkv);
-  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "attn: ", name, " must be bf16");
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(0) == q.size(0) && qkv.size(1) == q.size(2) &&
-              qkv.size(2) == 3 && qkv.size(3) == q.size(1) && qkv.size(4) == q.size(3),
-              "attn: ", name, " must be (B,T,3,H,C) matching q (B,H,T,C)");
-}
-static void check_attn_bthc(const torch::Tensor& q, const torch::Tensor& x,
-                            const char* name) {
-  CHECK_GPU(x);
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "attn: ", name, " must be bf16");
-  TORCH_CHECK(x.dim() == 4 && x.size(0) == q.size(0) && x.size(1) == q.size(2) &&
-              x.size(2) == q.size(1) && x.size(3) == q.size(3),
-              "attn: ", name, " must be (B,T,H,C) matching q (B,H,T,C)");
-}
-static void check_attn_lse(const torch::Tensor& q, const torch::Tensor& lse) {
-  CHECK_GPU(lse);
-  TORCH_CHECK(lse.scalar_type() == torch::kFloat &&
-              lse.numel() == q.size(0) * q.size(1) * q.size(2),
-              "attn: lse must be fp32 (B,H,T)");
+  return {c.dim(q, 0), c.dim(q, 1), c.dim(q, 2), c.dim(q, 3), qp, kp, q.options()};
 }
 
 // In-kernel dropout (philox.h). Without it the kernels (DROP = false) take
@@ -401,18 +451,11 @@ static MaybeDrop drop_if(double p, int64_t seed) {  // p == 0: no dropout
 // f(C, NW, DROP) as integral constants, for head dim 64|128 and 4|8 waves.
 template <typename F>
 static void dispatch_attn(int C, int NW, bool drop, F&& f) {
-  auto on_drop = [&](auto c, auto nw) {
-    if (drop) f(c, nw, std::true_type{});
-    else f(c, nw, std::false_type{});
-  };
-  using c64 = std::integral_constant<int, 64>;
-  using c128 = std::integral_constant<int, 128>;
-  using w4 = std::integral_constant<int, 4>;
-  using w8 = std::integral_constant<int, 8>;
-  if (C == 128 && NW == 8) on_drop(c128{}, w8{});
-  else if (C == 128) on_drop(c128{}, w4{});
-  else if (NW == 8) on_drop(c64{}, w8{});
-  else on_drop(c64{}, w4{});
+  dispatch_int<128, 64>(C, [&](auto c) {
+    dispatch_int<8, 4>(NW, [&](auto nw) {
+      dispatch_flag(drop, [&](auto dr) { f(c, nw, dr); });
+    });
+  });
 }
 
 // One forward launcher for every layout: v is read and o written through
@@ -420,16 +463,13 @@ static void dispatch_attn(int C, int NW, bool drop, F&& f) {
 // per wave, SPW = 1 (the kernels wait on memory, so wave co-residency matters
 // most); 4 waves for T % 256 != 0.
 // The paired-tile kernel is +4% at C=128 and -4% at C=64: C=128 only.
-static void attn_fwd_launch(torch::Tensor q, torch::Tensor k, const u16* vp,
-                            AttnStrides sv, u16* op, AttnStrides so,
-                            torch::Tensor lse, const MaybeDrop& drop) {
-  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
+static void attn_fwd_launch(const AttnQK& a, const u16* vp, AttnStrides sv, u16* op,
+                            AttnStrides so, float* lsep, const MaybeDrop& drop) {
+  const int B = a.B, H = a.H, T = a.T;
   const int NW = (T % 256 == 0) ? 8 : 4;
   const long grid = (long)B * H * (T / (NW * 32));
   const DropArgs d = drop.value_or(DropArgs{});
-  const u16 *qp = (const u16*)q.data_ptr(), *kp = (const u16*)k.data_ptr();
-  float* lsep = lse.data_ptr<float>();
-  dispatch_attn(C, NW, drop.has_value(), [&](auto c, auto nw, auto dr) {
+  dispatch_attn(a.C, NW, drop.has_value(), [&](auto c, auto nw, auto dr) {
     constexpr int CC = decltype(c)::value, NN = decltype(nw)::value;
     constexpr bool DROP = decltype(dr)::value;
     constexpr bool PAIRED = CC == 128 && NN == 8 && !DROP;
@@ -438,10 +478,10 @@ static void attn_fwd_launch(torch::Tensor q, torch::Tensor k, const u16* vp,
     const size_t smem = std::max((size_t)((PAIRED ? 8 : 4) * 32 * CC * 2),
                                  (size_t)(NN * 32 * 32 * 4));
     if constexpr (PAIRED)
-      launch(attn_fwd2_kernel<CC, NN>, grid, NN * 64, smem, qp, kp, vp, op, lsep,
+      launch(attn_fwd2_kernel<CC, NN>, grid, NN * 64, smem, a.q, a.k, vp, op, lsep,
              B, H, T, sv, so);
     else
-      launch(attn_fwd_kernel<CC, NN, 1, DROP>, grid, NN * 64, smem, qp, kp, vp, op, lsep,
+      launch(attn_fwd_kernel<CC, NN, 1, DROP>, grid, NN * 64, smem, a.q, a.k, vp, op, lsep,
              B, H, T, sv, so, d.seed_lo, d.seed_hi, d.thr, d.inv_keep);
   });
 }
@@ -449,23 +489,23 @@ static void attn_fwd_launch(torch::Tensor q, torch::Tensor k, const u16* vp,
 // One backward launcher for every layout: dO, v, o are read and dv written
 // through strides. do_copy: see attn_bwd_packed. Returns {dq, dk} (B,H,T,C).
 static std::vector<torch::Tensor> attn_bwd_launch(
-    const u16* dop, AttnStrides sdo, torch::Tensor q, torch::Tensor k,
-    const u16* vp, AttnStrides sv, const u16* op, AttnStrides so,
-    torch::Tensor lse, u16* dvp, AttnStrides sdv, const MaybeDrop& drop,
-    u16* do_copy = nullptr) {
-  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
-  long N = (long)B * H * T;
-  auto delta = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
+    const AttnQK& a, const u16* dop, AttnStrides sdo, const u16* vp, AttnStrides sv,
+    const u16* op, AttnStrides so, const float* lsep, u16* dvp, AttnStrides sdv,
+    const MaybeDrop& drop, u16* do_copy = nullptr) {
+  const int B = a.B, H = a.H, T = a.T, C = a.C;
+  const long N = a.rows();
   TORCH_CHECK(N < (1L << 31), "attn: B*H*T must be below 2^31");
+  auto delta = torch::empty({B, H, T}, a.opt.dtype(torch::kFloat));
+  const float* deltap = fresh<float>(delta);
   long dgrid = std::min((N + 3) / 4, (long)8192);
-  launch(attn_delta_kernel, dgrid, 256, 0, dop, op, delta.data_ptr<float>(), N, C, H, T,
+  launch(attn_delta_kernel, dgrid, 256, 0, dop, op, fresh<float>(delta), N, C, H, T,
          sdo, so, do_copy, (int)(sdo.h < sdo.r));
   if (do_copy) {  // the delta kernel left dO as packed (B,H,T,C) there
     dop = do_copy;
     sdo = strides_bhtc(H, T, C);
   }
-  auto dq = torch::empty_like(q);
-  auto dk = torch::empty_like(k);
+  auto dq = torch::empty({B, H, T, C}, a.opt);
+  auto dk = torch::empty({B, H, T, C}, a.opt);
   // MIDGPT_ATTN_DKV_NW4=1 (read once): 4-wave workgroups for the undropped
   // dkv and dq kernels at every T. Faster at C=64, slower at C=128
   // (profiles/launch_refactor.md).
@@ -473,8 +513,6 @@ static std::vector<torch::Tensor> attn_bwd_launch(
   const int NW = (T % 256 == 0 && !(nw4 && !drop)) ? 8 : 4;
   const long grid = (long)B * H * (T / (NW * 32));
   const DropArgs d = drop.value_or(DropArgs{});
-  const u16 *qp = (const u16*)q.data_ptr(), *kp = (const u16*)k.data_ptr();
-  const float *lsep = lse.data_ptr<float>(), *deltap = delta.data_ptr<float>();
   dispatch_attn(C, NW, drop.has_value(), [&](auto c, auto nw, auto dr) {
     constexpr int CC = decltype(c)::value, NN = decltype(nw)::value;
     constexpr bool DROP = decltype(dr)::value;
@@ -484,11 +522,11 @@ static std::vector<torch::Tensor> attn_bwd_launch(
                                      (size_t)(NN * 32 * 32 * 4));
     const size_t smem_dq = std::max((size_t)(2 * 3 * 32 * CC) * 2 + NN * 32 * 32 * 2,
                                     (size_t)(NN * 32 * 32 * 4));
-    launch(attn_bwd_dkv_kernel<CC, NN, DROP>, grid, NN * 64, smem_dkv, dop, qp, kp, vp,
-           lsep, deltap, (u16*)dk.data_ptr(), dvp, B, H, T, sdo, sv, sdv,
+    launch(attn_bwd_dkv_kernel<CC, NN, DROP>, grid, NN * 64, smem_dkv, dop, a.q, a.k, vp,
+           lsep, deltap, fresh<u16>(dk), dvp, B, H, T, sdo, sv, sdv,
            d.seed_lo, d.seed_hi, d.thr, d.inv_keep);
-    launch(attn_bwd_dq_kernel<CC, NN, 1, DROP>, grid, NN * 64, smem_dq, dop, qp, kp, vp,
-           lsep, deltap, (u16*)dq.data_ptr(), B, H, T, sdo, sv,
+    launch(attn_bwd_dq_kernel<CC, NN, 1, DROP>, grid, NN * 64, smem_dq, dop, a.q, a.k, vp,
+           lsep, deltap, fresh<u16>(dq), B, H, T, sdo, sv,
            d.seed_lo, d.seed_hi, d.thr, d.inv_keep);
   });
   return {dq, dk};
@@ -496,52 +534,50 @@ static std::vector<torch::Tensor> attn_bwd_launch(
 
 // ---------------------------------------------------------------------------
 // Entry points, (B,H,T,C) throughout.
-static std::vector<torch::Tensor> attn_fwd_bhtc(torch::Tensor q, torch::Tensor k,
-                                                torch::Tensor v, const MaybeDrop& drop) {
-  check_attn_qk(q, k);
-  check_attn_bhtc(q, v, "v");
-  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
+static std::vector<torch::Tensor> attn_fwd_bhtc(const char* who, torch::Tensor q,
+                                                torch::Tensor k, torch::Tensor v,
+                                                const MaybeDrop& drop) {
+  Call c(who, q);
+  const AttnQK a = attn_qk(c, q, k);
+  const u16* vp = c.bf16(v, "v", q.sizes());
   auto o = torch::empty_like(q);
-  auto lse = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
-  const AttnStrides st = strides_bhtc(H, T, C);
-  attn_fwd_launch(q, k, (const u16*)v.data_ptr(), st, (u16*)o.data_ptr(), st, lse, drop);
+  auto lse = torch::empty({a.B, a.H, a.T}, q.options().dtype(torch::kFloat));
+  const AttnStrides st = strides_bhtc(a.H, a.T, a.C);
+  attn_fwd_launch(a, vp, st, fresh<u16>(o), st, fresh<float>(lse), drop);
   return {o, lse};
 }
 
-static std::vector<torch::Tensor> attn_bwd_bhtc(torch::Tensor dO, torch::Tensor q,
-                                                torch::Tensor k, torch::Tensor v,
-                                                torch::Tensor o, torch::Tensor lse,
-                                                const MaybeDrop& drop) {
-  check_attn_qk(q, k);
-  check_attn_bhtc(q, v, "v");
-  check_attn_bhtc(q, o, "o");
-  check_attn_bhtc(q, dO, "dO");
-  check_attn_lse(q, lse);
-  int H = q.size(1), T = q.size(2), C = q.size(3);
+static std::vector<torch::Tensor> attn_bwd_bhtc(const char* who, torch::Tensor dO,
+                                                torch::Tensor q, torch::Tensor k,
+                                                torch::Tensor v, torch::Tensor o,
+                                                torch::Tensor lse, const MaybeDrop& drop) {
+  Call c(who, dO);
+  const AttnQK a = attn_qk(c, q, k);
+  const u16 *vp = c.bf16(v, "v", q.sizes()), *op = c.bf16(o, "o", q.sizes());
+  const u16* dop = c.bf16(dO, "dO", q.sizes());
+  const float* lsep = c.f32(lse, "lse", flat(a.rows()));
   auto dv = torch::empty_like(v);
-  const AttnStrides st = strides_bhtc(H, T, C);
-  auto r = attn_bwd_launch((const u16*)dO.data_ptr(), st, q, k, (const u16*)v.data_ptr(),
-                           st, (const u16*)o.data_ptr(), st, lse, (u16*)dv.data_ptr(), st,
-                           drop);
+  const AttnStrides st = strides_bhtc(a.H, a.T, a.C);
+  auto r = attn_bwd_launch(a, dop, st, vp, st, op, st, lsep, fresh<u16>(dv), st, drop);
   return {r[0], r[1], dv};
 }
 
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v) {
-  return attn_fwd_bhtc(q, k, v, MaybeDrop());
+  return attn_fwd_bhtc("attn_fwd", q, k, v, MaybeDrop());
 }
 std::vector<torch::Tensor> attn_bwd(torch::Tensor dO, torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, torch::Tensor o, torch::Tensor lse) {
-  return attn_bwd_bhtc(dO, q, k, v, o, lse, MaybeDrop());
+  return attn_bwd_bhtc("attn_bwd", dO, q, k, v, o, lse, MaybeDrop());
 }
 std::vector<torch::Tensor> attn_fwd_dropout(torch::Tensor q, torch::Tensor k,
                                             torch::Tensor v, double p, int64_t seed) {
-  return attn_fwd_bhtc(q, k, v, drop_args(p, seed));
+  return attn_fwd_bhtc("attn_fwd_dropout", q, k, v, drop_args(p, seed));
 }
 std::vector<torch::Tensor> attn_bwd_dropout(torch::Tensor dO, torch::Tensor q,
                                             torch::Tensor k, torch::Tensor v,
                                             torch::Tensor o, torch::Tensor lse,
                                             double p, int64_t seed) {
-  return attn_bwd_bhtc(dO, q, k, v, o, lse, drop_args(p, seed));
+  return attn_bwd_bhtc("attn_bwd_dropout", dO, q, k, v, o, lse, drop_args(p, seed));
 }
 
 // ---------------------------------------------------------------------------
@@ -550,28 +586,25 @@ std::vector<torch::Tensor> attn_bwd_dropout(torch::Tensor dO, torch::Tensor q,
 // slot 2 of a caller-supplied (B,T,3,H,C) dqkv. v is either the (B,H,T,C)
 // copy or the packed (B,T,3,H,C) projection itself, read in place from slot 2.
 // p == 0: no dropout.
-static const u16* packed_or_plain_v(const torch::Tensor& q, const torch::Tensor& v,
+static const u16* packed_or_plain_v(const Call& c, const AttnQK& a, const torch::Tensor& v,
                                     AttnStrides* sv) {
-  int H = q.size(1), T = q.size(2), C = q.size(3);
   if (v.dim() == 5) {
-    check_attn_packed(q, v, "qkv");
-    *sv = strides_qkv_slot(H, T, C);
-    return (const u16*)v.data_ptr() + 2L * H * C;
+    *sv = strides_qkv_slot(a.H, a.T, a.C);
+    return c.bf16(v, "qkv", {a.B, a.T, 3, a.H, a.C}) + 2L * a.H * a.C;
   }
-  check_attn_bhtc(q, v, "v");
-  *sv = strides_bhtc(H, T, C);
-  return (const u16*)v.data_ptr();
+  *sv = strides_bhtc(a.H, a.T, a.C);
+  return c.bf16(v, "v", {a.B, a.H, a.T, a.C});
 }
 
 std::vector<torch::Tensor> attn_fwd_packed(torch::Tensor q, torch::Tensor k,
                                            torch::Tensor v, double p, int64_t seed) {
-  check_attn_qk(q, k);
+  Call c("attn_fwd_packed", q);
+  const AttnQK a = attn_qk(c, q, k);
   AttnStrides sv;
-  const u16* vp = packed_or_plain_v(q, v, &sv);
-  int B = q.size(0), H = q.size(1), T = q.size(2), C = q.size(3);
-  auto o = torch::empty({B, T, H, C}, q.options());
-  auto lse = torch::empty({B, H, T}, q.options().dtype(torch::kFloat));
-  attn_fwd_launch(q, k, vp, sv, (u16*)o.data_ptr(), strides_bthc(H, T, C), lse,
+  const u16* vp = packed_or_plain_v(c, a, v, &sv);
+  auto o = torch::empty({a.B, a.T, a.H, a.C}, q.options());
+  auto lse = torch::empty({a.B, a.H, a.T}, q.options().dtype(torch::kFloat));
+  attn_fwd_launch(a, vp, sv, fresh<u16>(o), strides_bthc(a.H, a.T, a.C), fresh<float>(lse),
                   drop_if(p, seed));
   return {o, lse};
 }
@@ -583,30 +616,29 @@ std::vector<torch::Tensor> attn_bwd_packed(torch::Tensor dO, torch::Tensor q,
                                            torch::Tensor o, torch::Tensor lse,
                                            torch::Tensor dqkv, double p, int64_t seed,
                                            bool stage_do) {
-  check_attn_qk(q, k);
+  Call c("attn_bwd_packed", dO);
+  const AttnQK a = attn_qk(c, q, k);
+  const int B = a.B, H = a.H, T = a.T, C = a.C;
   AttnStrides sv;
-  const u16* vp = packed_or_plain_v(q, v, &sv);
-  check_attn_packed(q, dqkv, "dqkv");
-  check_attn_bthc(q, dO, "dO");
-  check_attn_bthc(q, o, "o");
-  check_attn_lse(q, lse);
-  int H = q.size(1), T = q.size(2), C = q.size(3);
-  u16* dvp = (u16*)dqkv.data_ptr() + 2L * H * C;
+  const u16* vp = packed_or_plain_v(c, a, v, &sv);
+  u16* dvp = c.bf16_out(dqkv, "dqkv", {B, T, 3, H, C}) + 2L * H * C;
+  const u16 *dop = c.bf16(dO, "dO", {B, T, H, C}), *op = c.bf16(o, "o", {B, T, H, C});
+  const float* lsep = c.f32(lse, "lse", flat(a.rows()));
   const AttnStrides sdv = strides_qkv_slot(H, T, C), so = strides_bthc(H, T, C);
   torch::Tensor do_copy;
   if (stage_do) do_copy = torch::empty_like(q);
-  return attn_bwd_launch((const u16*)dO.data_ptr(), so, q, k, vp, sv,
-                         (const u16*)o.data_ptr(), so, lse, dvp, sdv, drop_if(p, seed),
-                         stage_do ? (u16*)do_copy.data_ptr() : nullptr);
+  return attn_bwd_launch(a, dop, so, vp, sv, op, so, lsep, dvp, sdv, drop_if(p, seed),
+                         stage_do ? fresh<u16>(do_copy) : nullptr);
 }
 
 // ---------------------------------------------------------------------------
+// idx[i] in [0, V) is the caller's contract: checking it would be a sync.
 torch::Tensor embedding_bwd(torch::Tensor dy, torch::Tensor idx, long V) {
-  CHECK_GPU(dy); CHECK_GPU(idx);
-  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16, "embedding_bwd: dy bf16");
-  TORCH_CHECK(idx.scalar_type() == torch::kLong, "embedding_bwd: idx int64");
+  Call c("embedding_bwd", dy);
+  const u16* dyp = c.bf16(dy, "dy", {ANY, ANY});
   long N = dy.size(0);
-  int D = dy.size(1);
+  int D = c.dim(dy, 1);
+  const long* ip = c.i64(idx, "idx", {N});
   TORCH_CHECK(D % 8 == 0, "embedding_bwd: D % 8 == 0");
   if (D % 64 == 0) {
     // sort-based run-per-wave accumulation (exact fp32, no atomics)
@@ -617,68 +649,58 @@ torch::Tensor embedding_bwd(torch::Tensor dy, torch::Tensor idx, long V) {
     const int wpb = 4;  // waves per block
     long grid = (N + wpb - 1) / wpb;
     for (int d0 = 0; d0 < D; d0 += 2048)
-      hipLaunchKernelGGL(embed_bwd_sorted_kernel, dim3(grid), dim3(wpb * 64),
-                         0, cur_stream(), (const u16*)dy.data_ptr(),
-                         sorted.data_ptr<long>(), perm.data_ptr<long>(),
-                         (u16*)dw.data_ptr(), N, D, d0);
-    launch_check();
+      launch(embed_bwd_sorted_kernel, grid, wpb * 64, 0, dyp, fresh<long>(sorted),
+             fresh<long>(perm), fresh<u16>(dw), N, D, d0);
     return dw;
   }
   auto dw32 = torch::zeros({V, (long)D}, dy.options().dtype(torch::kFloat));
   long grid = std::min(N, (long)4096);
-  hipLaunchKernelGGL(embed_bwd_scatter_kernel, dim3(grid), dim3(256), 0,
-                     cur_stream(), (const u16*)dy.data_ptr(),
-                     idx.data_ptr<long>(), dw32.data_ptr<float>(), N, D);
-  launch_check();
+  launch(embed_bwd_scatter_kernel, grid, 256, 0, dyp, ip, fresh<float>(dw32), N, D);
   auto dw = torch::empty({V, (long)D}, dy.options());
   long n = V * (long)D;
   long cgrid = std::min((n / 4 + 255) / 256 + 1, (long)4096);
-  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(cgrid), dim3(256), 0,
-                     cur_stream(), dw32.data_ptr<float>(), (u16*)dw.data_ptr(), n);
-  launch_check();
+  launch(f32_to_bf16_kernel, cgrid, 256, 0, fresh<float>(dw32), fresh<u16>(dw), n);
   return dw;
 }
 
 // ---------------------------------------------------------------------------
 torch::Tensor gelu_fwd(torch::Tensor x) {
-  CHECK_GPU(x);
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.numel() % 8 == 0,
-              "gelu: bf16 with numel %% 8 == 0");
-  auto y = torch::empty_like(x);
+  Call c("gelu_fwd", x);
   long n = x.numel();
+  const u16* xp = c.bf16(x, "x", flat(n));
+  TORCH_CHECK(n % 8 == 0, "gelu_fwd: numel % 8 == 0 required");
+  auto y = torch::empty_like(x);
   long grid = std::min((n / 8 + 255) / 256 + 1, (long)8192);
-  hipLaunchKernelGGL(gelu_fwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const u16*)x.data_ptr(), (u16*)y.data_ptr(), n);
-  launch_check();
+  launch(gelu_fwd_bf16, grid, 256, 0, xp, fresh<u16>(y), n);
   return y;
 }
 
 torch::Tensor gelu_bwd(torch::Tensor dy, torch::Tensor x) {
-  CHECK_GPU(dy); CHECK_GPU(x);
-  auto dx = torch::empty_like(x);
+  Call c("gelu_bwd", dy);
   long n = x.numel();
+  const u16 *xp = c.bf16(x, "x", flat(n)), *dyp = c.bf16(dy, "dy", flat(n));
+  TORCH_CHECK(n % 8 == 0, "gelu_bwd: numel % 8 == 0 required");
+  auto dx = torch::empty_like(x);
   long grid = std::min((n / 8 + 255) / 256 + 1, (long)8192);
-  hipLaunchKernelGGL(gelu_bwd_bf16, dim3(grid), dim3(256), 0, cur_stream(),
-                     (const u16*)dy.data_ptr(), (const u16*)x.data_ptr(),
-                     (u16*)dx.data_ptr(), n);
-  launch_check();
+  launch(gelu_bwd_bf16, grid, 256, 0, dyp, xp, fresh<u16>(dx), n);
   return dx;
 }
 
 // ---------------------------------------------------------------------------
-// KV-cache decode (decode.hip). Caches are (B,H,Tmax,C) bf16, contiguous.
-static void check_decode_cache(const torch::Tensor& k_cache, const torch::Tensor& v_cache,
-                               int B, int H, int C, const char* who) {
-  CHECK_GPU(k_cache); CHECK_GPU(v_cache);
-  TORCH_CHECK(k_cache.scalar_type() == torch::kBFloat16 &&
-              v_cache.scalar_type() == torch::kBFloat16, who, ": caches must be bf16");
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(0) == B && k_cache.size(1) == H &&
-              k_cache.size(3) == C && v_cache.sizes() == k_cache.sizes(),
-              who, ": caches must both be (B,H,Tmax,C)");
-  TORCH_CHECK(C == 64 || C == 128, who, ": head dim 64 or 128 (got ", C, ")");
+// KV-cache decode (decode.hip). Caches are (B,H,Tmax,C) bf16, contiguous;
+// returns Tmax.
+static int64_t decode_caches(const Call& c, const torch::Tensor& k_cache,
+                             const torch::Tensor& v_cache, int B, int H, int C, u16** kp,
+                             u16** vp) {
+  TORCH_CHECK(C == 64 || C == 128, c.who, ": head dim 64 or 128 (got ", C, ")");
+  *kp = c.bf16_out(k_cache, "k_cache", {B, H, ANY, C});
+  *vp = c.bf16_out(v_cache, "v_cache", k_cache.sizes());
+  return k_cache.size(2);
 }
 
 // Host copy of per-sequence positions or lengths: (B,) integers on the CPU.
+// The device copy, (B,) int32, is what the kernels read. The two are not
+// compared (that would be a sync): keeping them equal is the caller's contract.
 static std::vector<int64_t> host_lens(const torch::Tensor& t, int B, const char* who) {
   TORCH_CHECK(!t.is_cuda() && t.dim() == 1 && t.size(0) == B &&
               at::isIntegralType(t.scalar_type(), false),
@@ -688,35 +710,26 @@ static std::vector<int64_t> host_lens(const torch::Tensor& t, int B, const char*
   return std::vector<int64_t>(p, p + B);
 }
 
-// Device copy: (B,) int32 on the GPU, what the kernels read. Not compared
-// with the host copy (that would be a sync): keeping them equal is the
-// caller's contract.
-static const int* dev_lens(const torch::Tensor& t, int B, const char* who) {
-  CHECK_GPU(t);
-  TORCH_CHECK(t.scalar_type() == torch::kInt && t.dim() == 1 && t.size(0) == B,
-              who, ": the device copy must be (", B, ",) int32");
-  return t.data_ptr<int>();
-}
-
 // sin/cos are the FULL tables (rows >= pos+Tn, C/2) fp32; fp32 LN weights are
 // used in place, others converted. pos_dev == nullptr: every sequence at
 // pos[0]; otherwise sequence b at pos[b] (host) == pos_dev[b] (device).
-static torch::Tensor kv_append_impl(torch::Tensor qkv, torch::Tensor qw, torch::Tensor kw,
-                                    torch::Tensor sin_t, torch::Tensor cos_t,
+static torch::Tensor kv_append_impl(const Call& c, torch::Tensor qkv, torch::Tensor qw,
+                                    torch::Tensor kw, torch::Tensor sin_t, torch::Tensor cos_t,
                                     torch::Tensor k_cache, torch::Tensor v_cache,
                                     const std::vector<int64_t>& pos, const int* pos_dev,
                                     double eps) {
-  CHECK_GPU(qkv); CHECK_GPU(sin_t); CHECK_GPU(cos_t); CHECK_GPU(qw); CHECK_GPU(kw);
-  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "kv_append: qkv must be bf16");
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "kv_append: qkv must be (B,Tn,3,H,C)");
-  int B = qkv.size(0), Tn = qkv.size(1), H = qkv.size(3), C = qkv.size(4);
-  check_decode_cache(k_cache, v_cache, B, H, C, "kv_append");
-  const int64_t Tmax = k_cache.size(2);
+  const u16* qkvp = c.bf16(qkv, "qkv", {ANY, ANY, 3, ANY, ANY});
+  int B = c.dim(qkv, 0), Tn = c.dim(qkv, 1), H = c.dim(qkv, 3), C = c.dim(qkv, 4);
+  u16 *kcp, *vcp;
+  const int64_t Tmax = decode_caches(c, k_cache, v_cache, B, H, C, &kcp, &vcp);
   TORCH_CHECK(Tn >= 1, "kv_append: no new tokens");
-  TORCH_CHECK(qw.numel() == C && kw.numel() == C, "kv_append: LN weights must be (C,)");
-  TORCH_CHECK(sin_t.scalar_type() == torch::kFloat && cos_t.scalar_type() == torch::kFloat &&
-              sin_t.dim() == 2 && sin_t.size(1) == C / 2 && cos_t.sizes() == sin_t.sizes(),
-              "kv_append: sin/cos must be fp32 (rows, C/2)");
+  TORCH_CHECK(qw.is_contiguous() && kw.is_contiguous(),
+              "kv_append: LN weights must be contiguous");
+  auto qwf = qw.to(torch::kFloat);
+  auto kwf = kw.to(torch::kFloat);
+  const float *qwp = c.f32(qwf, "qw", flat(C)), *kwp = c.f32(kwf, "kw", flat(C));
+  const float* sinp = c.f32(sin_t, "sin", {ANY, C / 2});
+  const float* cosp = c.f32(cos_t, "cos", sin_t.sizes());
   for (int64_t p : pos) {
     TORCH_CHECK(p >= 0 && p + Tn <= Tmax, "kv_append: rows [", p, ", ", p + Tn,
                 ") do not fit a cache of ", Tmax, " rows");
@@ -724,23 +737,13 @@ static torch::Tensor kv_append_impl(torch::Tensor qkv, torch::Tensor qw, torch::
                 " rows, position ", p + Tn - 1, " needed");
   }
   auto q = torch::empty({B, H, Tn, C}, qkv.options());
-  auto qwf = qw.to(torch::kFloat);
-  auto kwf = kw.to(torch::kFloat);
   const long nrows = (long)B * Tn * H * 3;
   const int rpb = 4 * (WAVE / (C / 8));  // rows per 256-thread block
   const long grid = std::min((nrows + rpb - 1) / rpb, (long)16384);
-#define LAUNCH_APPEND(RAGGED)                                                     \
-  hipLaunchKernelGGL(kv_append_kernel<RAGGED>, dim3(grid), dim3(256), 0,          \
-                     cur_stream(), (const u16*)qkv.data_ptr(),                    \
-                     qwf.data_ptr<float>(), kwf.data_ptr<float>(),                \
-                     sin_t.data_ptr<float>(), cos_t.data_ptr<float>(),            \
-                     (u16*)q.data_ptr(), (u16*)k_cache.data_ptr(),                \
-                     (u16*)v_cache.data_ptr(), B, Tn, H, C, (long)Tmax,           \
-                     (long)pos[0], pos_dev, (float)eps)
-  if (pos_dev) LAUNCH_APPEND(true);
-  else LAUNCH_APPEND(false);
-#undef LAUNCH_APPEND
-  launch_check();
+  dispatch_flag(pos_dev != nullptr, [&](auto ragged) {
+    launch(kv_append_kernel<decltype(ragged)::value>, grid, 256, 0, qkvp, qwp, kwp, sinp, cosp,
+           fresh<u16>(q), kcp, vcp, B, Tn, H, C, (long)Tmax, (long)pos[0], pos_dev, (float)eps);
+  });
   return q;
 }
 
@@ -748,19 +751,21 @@ torch::Tensor kv_append(torch::Tensor qkv, torch::Tensor qw, torch::Tensor kw,
                         torch::Tensor sin_t, torch::Tensor cos_t,
                         torch::Tensor k_cache, torch::Tensor v_cache, int64_t pos,
                         double eps) {
-  return kv_append_impl(qkv, qw, kw, sin_t, cos_t, k_cache, v_cache, {pos}, nullptr, eps);
+  Call c("kv_append", qkv);
+  return kv_append_impl(c, qkv, qw, kw, sin_t, cos_t, k_cache, v_cache, {pos}, nullptr, eps);
 }
 
 torch::Tensor kv_append_ragged(torch::Tensor qkv, torch::Tensor qw, torch::Tensor kw,
                                torch::Tensor sin_t, torch::Tensor cos_t,
                                torch::Tensor k_cache, torch::Tensor v_cache,
                                torch::Tensor pos_dev, torch::Tensor pos_host, double eps) {
-  TORCH_CHECK(qkv.dim() == 5, "kv_append: qkv must be (B,Tn,3,H,C)");
-  const int B = qkv.size(0);
-  TORCH_CHECK(B >= 1, "kv_append: empty batch");
-  auto pos = host_lens(pos_host, B, "kv_append_ragged");
-  return kv_append_impl(qkv, qw, kw, sin_t, cos_t, k_cache, v_cache, pos,
-                        dev_lens(pos_dev, B, "kv_append_ragged"), eps);
+  Call c("kv_append_ragged", qkv);
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(0) >= 1,
+              "kv_append: qkv must be (B,Tn,3,H,C) with B >= 1");
+  const int B = c.dim(qkv, 0);
+  auto pos = host_lens(pos_host, B, c.who);
+  return kv_append_impl(c, qkv, qw, kw, sin_t, cos_t, k_cache, v_cache, pos,
+                        c.i32(pos_dev, "pos_dev", {B}), eps);
 }
 
 static int decode_cu_count() {
@@ -797,16 +802,14 @@ int64_t attn_decode_auto_splits(int64_t rows, int64_t kv_len, int64_t cus) {
 // sequence has kv_lens[0] positions; otherwise sequence b has kv_lens[b]
 // (host) == lens_dev[b] (device), and num_splits = 0 applies the rule to the
 // longest.
-static torch::Tensor attn_decode_impl(torch::Tensor q, torch::Tensor k_cache,
+static torch::Tensor attn_decode_impl(const Call& c, torch::Tensor q, torch::Tensor k_cache,
                                       torch::Tensor v_cache,
                                       const std::vector<int64_t>& kv_lens,
                                       const int* lens_dev, int64_t num_splits) {
-  CHECK_GPU(q);
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn_decode: q must be bf16");
-  TORCH_CHECK(q.dim() == 4, "attn_decode: q must be (B,H,Tq,C)");
-  int B = q.size(0), H = q.size(1), Tq = q.size(2), C = q.size(3);
-  check_decode_cache(k_cache, v_cache, B, H, C, "attn_decode");
-  const int64_t Tmax = k_cache.size(2);
+  const u16* qp = c.bf16(q, "q", {ANY, ANY, ANY, ANY});
+  int B = c.dim(q, 0), H = c.dim(q, 1), Tq = c.dim(q, 2), C = c.dim(q, 3);
+  u16 *kcp, *vcp;
+  const int64_t Tmax = decode_caches(c, k_cache, v_cache, B, H, C, &kcp, &vcp);
   int64_t kv_max = 0;
   for (int64_t kv_len : kv_lens) {
     TORCH_CHECK(kv_len <= Tmax, "attn_decode: kv_len ", kv_len, " exceeds the cache (", Tmax, ")");
@@ -829,59 +832,53 @@ static torch::Tensor attn_decode_impl(torch::Tensor q, torch::Tensor k_cache,
   if (S > 1) {
     ws_acc = torch::empty({rows, S, C}, q.options().dtype(torch::kFloat));
     ws_ml = torch::empty({rows, S, 2}, q.options().dtype(torch::kFloat));
-    accp = ws_acc.data_ptr<float>();
-    mlp = ws_ml.data_ptr<float>();
+    accp = fresh<float>(ws_acc);
+    mlp = fresh<float>(ws_ml);
   }
   const float scale = 1.0f / std::sqrt((float)C);
-#define LAUNCH_DECODE(CC, RAGGED)                                                 \
-  hipLaunchKernelGGL((attn_decode_kernel<CC, RAGGED>), dim3(rows, S), dim3(256), 0, \
-                     cur_stream(), (const u16*)q.data_ptr(),                      \
-                     (const u16*)k_cache.data_ptr(), (const u16*)v_cache.data_ptr(), \
-                     (u16*)o.data_ptr(), accp, mlp, H, Tq, (long)Tmax,            \
-                     (int)kv_lens[0], lens_dev, S, scale)
-  if (C == 128) { if (lens_dev) LAUNCH_DECODE(128, true); else LAUNCH_DECODE(128, false); }
-  else { if (lens_dev) LAUNCH_DECODE(64, true); else LAUNCH_DECODE(64, false); }
-#undef LAUNCH_DECODE
-  launch_check();
-  if (S > 1) {
-    hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(rows), dim3(C), 0, cur_stream(),
-                       accp, mlp, (u16*)o.data_ptr(), H, Tq, C, S);
-    launch_check();
-  }
+  dispatch_int<128, 64>(C, [&](auto cc) {
+    dispatch_flag(lens_dev != nullptr, [&](auto ragged) {
+      launch(attn_decode_kernel<decltype(cc)::value, decltype(ragged)::value>, dim3(rows, S),
+             256, 0, qp, kcp, vcp, fresh<u16>(o), accp, mlp, H, Tq, (long)Tmax,
+             (int)kv_lens[0], lens_dev, S, scale);
+    });
+  });
+  if (S > 1)
+    launch(attn_decode_combine_kernel, rows, C, 0, accp, mlp, fresh<u16>(o), H, Tq, C, S);
   return o;
 }
 
 torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
                           int64_t kv_len, int64_t num_splits) {
-  return attn_decode_impl(q, k_cache, v_cache, {kv_len}, nullptr, num_splits);
+  Call c("attn_decode", q);
+  return attn_decode_impl(c, q, k_cache, v_cache, {kv_len}, nullptr, num_splits);
 }
 
 torch::Tensor attn_decode_ragged(torch::Tensor q, torch::Tensor k_cache,
                                  torch::Tensor v_cache, torch::Tensor kv_lens_dev,
                                  torch::Tensor kv_lens_host, int64_t num_splits) {
-  TORCH_CHECK(q.dim() == 4, "attn_decode: q must be (B,H,Tq,C)");
-  const int B = q.size(0);
-  TORCH_CHECK(B >= 1, "attn_decode: empty batch");
-  auto lens = host_lens(kv_lens_host, B, "attn_decode_ragged");
-  return attn_decode_impl(q, k_cache, v_cache, lens,
-                          dev_lens(kv_lens_dev, B, "attn_decode_ragged"), num_splits);
+  Call c("attn_decode_ragged", q);
+  TORCH_CHECK(q.dim() == 4 && q.size(0) >= 1, "attn_decode: q must be (B,H,Tq,C) with B >= 1");
+  const int B = c.dim(q, 0);
+  auto lens = host_lens(kv_lens_host, B, c.who);
+  return attn_decode_impl(c, q, k_cache, v_cache, lens,
+                          c.i32(kv_lens_dev, "kv_lens_dev", {B}), num_splits);
 }
 
 // ---------------------------------------------------------------------------
+// The probe kernels read fixed extents: A (32,16) and B (16,32), M and B (32,32).
 torch::Tensor probe_mfma(torch::Tensor A, torch::Tensor B) {
-  CHECK_GPU(A); CHECK_GPU(B);
+  Call c("probe_mfma", A);
+  const float *ap = c.f32(A, "A", {32, 16}), *bp = c.f32(B, "B", {16, 32});
   auto D = torch::zeros({32, 32}, A.options());
-  hipLaunchKernelGGL(probe_mfma_kernel, dim3(1), dim3(64), 0, cur_stream(),
-                     A.data_ptr<float>(), B.data_ptr<float>(), D.data_ptr<float>());
-  launch_check();
+  launch(probe_mfma_kernel, 1, 64, 0, ap, bp, fresh<float>(D));
   return D;
 }
 torch::Tensor probe_pack(torch::Tensor M, torch::Tensor B) {
-  CHECK_GPU(M); CHECK_GPU(B);
+  Call c("probe_pack", M);
+  const float *mp = c.f32(M, "M", {32, 32}), *bp = c.f32(B, "B", {32, 32});
   auto D = torch::zeros({32, 32}, M.options());
-  hipLaunchKernelGGL(probe_pack_kernel, dim3(1), dim3(64), 0, cur_stream(),
-                     M.data_ptr<float>(), B.data_ptr<float>(), D.data_ptr<float>());
-  launch_check();
+  launch(probe_pack_kernel, 1, 64, 0, mp, bp, fresh<float>(D));
   return D;
 }
 

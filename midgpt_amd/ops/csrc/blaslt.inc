@@ -114,17 +114,19 @@ static void lt_matmul(int64_t m, int64_t n, int64_t k,
 
 // dh(M,N) = dgelu(dy(M,N2) @ w2(N2,N), aux = h(M,N))
 torch::Tensor matmul_dgelu(torch::Tensor dy, torch::Tensor w2, torch::Tensor h) {
-  CHECK_GPU(dy); CHECK_GPU(w2); CHECK_GPU(h);
-  const int64_t M = dy.size(0), N2 = dy.size(1), N = w2.size(1);
-  TORCH_CHECK(w2.size(0) == N2 && h.size(0) == M && h.size(1) == N);
+  Call c("matmul_dgelu", dy);
+  const u16* dyp = c.bf16(dy, "dy", {ANY, ANY});
+  const int64_t M = dy.size(0), N2 = dy.size(1);
+  const u16* w2p = c.bf16(w2, "w2", {N2, ANY});
+  const int64_t N = w2.size(1);
+  u16* hp = c.bf16_out(h, "h", {M, N});  // read only; the aux pointer is void*
   auto dh = torch::empty({M, N}, dy.options());
   auto ws = torch::empty({(long)blaslt::WORKSPACE},
                          dy.options().dtype(torch::kUInt8));
   // col-major: DH_cm(N,M) = W2_cm(N,N2) x DY_cm(N2,M)
-  blaslt::lt_matmul(N, M, N2, w2.data_ptr(), HIPBLAS_OP_N, N,
-                    dy.data_ptr(), HIPBLAS_OP_N, N2, dh.data_ptr(), N,
-                    HIPBLASLT_EPILOGUE_DGELU, h.data_ptr(), N,
-                    ws.data_ptr(), cur_stream());
+  blaslt::lt_matmul(N, M, N2, w2p, HIPBLAS_OP_N, N, dyp, HIPBLAS_OP_N, N2,
+                    fresh<u16>(dh), N, HIPBLASLT_EPILOGUE_DGELU, hp, N,
+                    fresh<uint8_t>(ws), cur_stream());
   return dh;
 }
 

@@ -216,16 +216,25 @@ def decode_stepper(model, batch_size: int):
 @torch.no_grad()
 def generate(model, idx: torch.Tensor, max_new_tokens: int,
              temperature: float = 1.0, top_k: int | None = None,
-             generator: torch.Generator | None = None) -> torch.Tensor:
-    """idx (B, T0) int64 -> (B, T0 + max_new_tokens)."""
+             generator: torch.Generator | None = None,
+             seed: int | None = None) -> torch.Tensor:
+    """idx (B, T0) int64 -> (B, T0 + max_new_tokens).
+
+    With ``seed`` (and temperature > 0) token t of the call, counted from 0
+    through a slid window too, is ``ops.sample_tokens(logits, temperature,
+    top_k, seed=seed, step=t)`` with row = batch index: one launch per token
+    on the native path, no host round trip, the same text on the CPU and on
+    the GPU wherever the logits agree. Without it the draw is
+    ``torch.multinomial`` from ``generator`` or the global RNG."""
+    _check_seed(seed, generator)
     model.eval()
     block = model.config.block_size
     step = decode_stepper(model, idx.shape[0])
     # prompts longer than block_size condition on the last block_size tokens
     # (reference sample.py:74-81 crops to the trailing window)
     logits = step(idx[:, -block:], 0)
-    for _ in range(max_new_tokens):
-        nxt = _sample(logits, temperature, top_k, generator)
+    for t in range(max_new_tokens):
+        nxt = _next_token(logits, temperature, top_k, generator, seed, t)
         idx = torch.cat([idx, nxt[:, None]], dim=1)
         if idx.shape[1] <= block:
             logits = step(nxt[:, None], idx.shape[1] - 1)
@@ -368,7 +377,7 @@ def decode_step_ragged(model, idx_new: torch.Tensor, cache: KVCache) -> torch.Te
 def generate_ragged(model, prompts, max_new_tokens: int, temperature: float = 1.0,
                     top_k: int | None = None, eos_id: int | None = None,
                     generator: torch.Generator | None = None,
-                    stop_check_every: int = 16) -> list:
+                    stop_check_every: int = 16, seed: int | None = None) -> list:
     """Decode a batch of prompts of different lengths together: ``prompts`` is
     a list of 1-D int64 tensors; returns, per prompt, the prompt plus what it
     generated, cut after its first ``eos_id`` if that is set.
@@ -384,8 +393,12 @@ def generate_ragged(model, prompts, max_new_tokens: int, temperature: float = 1.
     every ``stop_check_every`` steps; a parameter, not a measured optimum)
     finds every sequence done.
 
+    ``seed`` as in ``generate``: step t of the loop draws with
+    ``ops.sample_tokens(..., seed=seed, step=t)``, row = index of the prompt.
+
     Native under ``native_decode(model)``; otherwise the same code runs on
     ``ops.ref_backend`` with fp32 caches."""
+    _check_seed(seed, generator)
     model.eval()
     block = model.config.block_size
     dev = model.wte.device
@@ -404,7 +417,7 @@ def generate_ragged(model, prompts, max_new_tokens: int, temperature: float = 1.
     budget_dev = torch.tensor(budget, device=dev)
     done = torch.zeros(B, dtype=torch.bool, device=dev)
     for t in range(n_steps):
-        nxt = _sample(logits, temperature, top_k, generator)
+        nxt = _next_token(logits, temperature, top_k, generator, seed, t)
         toks[:, t] = nxt
         if t + 1 == n_steps:
             break
@@ -423,6 +436,20 @@ def generate_ragged(model, prompts, max_new_tokens: int, temperature: float = 1.
                 new = new[:int(hit[0]) + 1]
         out.append(torch.cat([p, new.to(p.device)]))
     return out
+
+
+def _check_seed(seed, generator):
+    if seed is not None and generator is not None:
+        raise ValueError("pass seed= (counter-based sampling) or generator= "
+                         "(torch.multinomial), not both")
+
+
+def _next_token(logits, temperature, top_k, generator, seed, t):
+    """Token t of a call: seeded sampling where a seed is given, ``_sample``
+    otherwise; greedy (temperature <= 0) is argmax either way."""
+    if seed is None or temperature <= 0:
+        return _sample(logits, temperature, top_k, generator)
+    return ops.sample_tokens(logits, temperature, top_k, seed=seed, step=t)
 
 
 def _sample(logits, temperature, top_k, generator):

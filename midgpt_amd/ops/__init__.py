@@ -9,6 +9,7 @@ to explicitly run the reference path on GPU (debugging only).
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -30,6 +31,8 @@ BACKEND_API = (
 # The ragged decode pair (per-sequence positions / lengths), implemented by
 # both backends under the same rule as BACKEND_API.
 RAGGED_API = ("kv_append_ragged", "attn_decode_ragged")
+# Seeded token sampling, under the same rule.
+SAMPLING_API = ("sample_tokens",)
 
 
 def _try_load_ext():
@@ -248,10 +251,15 @@ def _resolve_dropout(dropout_p, seed, who):
         raise ValueError(f"{who}: dropout_p must be in [0, 1), got {dropout_p}")
     if seed is None:
         seed = draw_dropout_seed()
+    return dropout_p, _seed_i64(seed)
+
+
+def _seed_i64(seed) -> int:
+    """The low 64 bits of ``seed`` as the int64 the bindings take."""
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    if seed >= 1 << 63:  # the binding takes the same 64 bits as an int64
+    if seed >= 1 << 63:
         seed -= 1 << 64
-    return dropout_p, seed
+    return seed
 
 
 # ----------------------------------------------------------------------------
@@ -446,6 +454,52 @@ def prefill_attention(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
     k_cache[:, :, :Tn].copy_(k[:, :, :Tn])
     v_cache[:, :, :Tn].copy_(v[:, :, :Tn])
     return o[:, :Tn].reshape(B, Tn, H * C)
+
+
+# ----------------------------------------------------------------------------
+# Seeded token sampling (inference only): one token per row of logits, a pure
+# function of (seed, step, row, logits), so the same seed gives the same draw
+# on the CPU and on the GPU and nothing crosses to the host. GPU, contiguous
+# bf16: csrc/sampling.hip, one launch. Everything else (fp32 logits, strided
+# logits, the CPU, MIDGPT_FORCE_REF=1): ref_backend, the same definition.
+# ----------------------------------------------------------------------------
+def sample_tokens(logits, temperature: float, top_k: int | None = None, *,
+                  seed: int, step: int):
+    """logits (B, V) -> tokens (B,) int64 drawn from
+    softmax(logits / temperature), restricted with ``top_k`` to the entries
+    >= the row's k-th largest logit (ties with it kept; None, 0 or >= V: all).
+
+    Gumbel-max with counter-based noise: entry v of row b at token ``step``
+    (in [0, 2^32)) takes a Philox word keyed by the 64-bit ``seed`` at counter
+    (v >> 2, b, step), see csrc/philox.h. The draw of a row therefore depends
+    on its index in the batch. ``temperature`` must be > 0: greedy decoding is
+    ``argmax``, not a mode of this op."""
+    temperature = float(temperature)
+    if not temperature > 0.0:
+        raise ValueError(f"sample_tokens: temperature must be > 0, got {temperature}")
+    # fp32(1/T), computed once, is what every backend multiplies by
+    inv_t = torch.tensor(1.0 / temperature, dtype=torch.float32).item()
+    if not (math.isfinite(inv_t) and inv_t > 0.0):
+        raise ValueError(f"sample_tokens: 1/temperature is {inv_t} in fp32")
+    top_k = 0 if top_k is None else int(top_k)
+    if top_k < 0:
+        raise ValueError(f"sample_tokens: top_k must be >= 0, got {top_k}")
+    step = int(step)
+    if not 0 <= step < 1 << 32:
+        raise ValueError(f"sample_tokens: step must be in [0, 2^32), got {step}")
+    if logits.dim() != 2:
+        raise ValueError(f"sample_tokens: logits must be (B, V), got {tuple(logits.shape)}")
+    impl = _backend(logits)
+    if logits.dtype != torch.bfloat16 or not logits.is_contiguous():
+        impl = ref_backend
+    return impl.sample_tokens(logits, inv_t, top_k, _seed_i64(seed), step)
+
+
+def draw_sample_seed() -> int:
+    """A seed for ``sample_tokens`` from torch's default CPU generator, as
+    ``draw_dropout_seed`` draws one: no device sync, reproducible under
+    torch.manual_seed."""
+    return draw_dropout_seed()
 
 
 # ----------------------------------------------------------------------------

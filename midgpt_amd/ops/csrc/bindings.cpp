@@ -866,6 +866,31 @@ torch::Tensor attn_decode_ragged(torch::Tensor q, torch::Tensor k_cache,
 }
 
 // ---------------------------------------------------------------------------
+// One token per row of logits (sampling.hip). top_k: 0 or >= V means all.
+torch::Tensor sample_tokens(torch::Tensor logits, double inv_t, int64_t top_k, int64_t seed,
+                            int64_t step) {
+  Call c("sample_tokens", logits);
+  const u16* lp = c.bf16(logits, "logits", {ANY, ANY});
+  const int B = c.dim(logits, 0), V = c.dim(logits, 1);
+  TORCH_CHECK(V >= 1, "sample_tokens: empty rows");
+  const float it = (float)inv_t;
+  TORCH_CHECK(std::isfinite(inv_t) && std::isfinite(it) && it > 0.f,
+              "sample_tokens: inv_t must be finite and > 0, got ", inv_t);
+  TORCH_CHECK(top_k >= 0, "sample_tokens: top_k >= 0 required (0: all), got ", top_k);
+  TORCH_CHECK(step >= 0 && step <= (int64_t)UINT32_MAX,
+              "sample_tokens: step must be in [0, 2^32), got ", step);
+  auto out = torch::empty({(long)B}, logits.options().dtype(torch::kLong));
+  const bool has_k = top_k >= 1 && top_k < V;
+  const uint64_t s = (uint64_t)seed;
+  dispatch_flag(has_k, [&](auto hk) {
+    launch(sample_tokens_kernel<decltype(hk)::value>, B, SAMPLE_THREADS, 0, lp,
+           fresh<long>(out), V, it, has_k ? (int)top_k : 0, (uint32_t)s, (uint32_t)(s >> 32),
+           (uint32_t)step);
+  });
+  return out;
+}
+
+// ---------------------------------------------------------------------------
 // The probe kernels read fixed extents: A (32,16) and B (16,32), M and B (32,32).
 torch::Tensor probe_mfma(torch::Tensor A, torch::Tensor B) {
   Call c("probe_mfma", A);
@@ -920,6 +945,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("num_splits") = 0);
   mod.def("attn_decode_auto_splits", &attn_decode_auto_splits, py::arg("rows"),
           py::arg("kv_len"), py::arg("cus"));
+  mod.def("sample_tokens", &sample_tokens, py::arg("logits"), py::arg("inv_t"),
+          py::arg("top_k"), py::arg("seed"), py::arg("step"));
   mod.def("embedding_bwd", &embedding_bwd);
   mod.def("gelu_fwd", &gelu_fwd);
   mod.def("gelu_bwd", &gelu_bwd);

@@ -8,5 +8,6 @@
 #include "decode.hip"
 #include "embedding.hip"
 #include "gelu.hip"
+#include "sampling.hip"
 #include "probe.hip"
 #include "bindings.cpp"

@@ -60,6 +60,15 @@ PHILOX_INL PhiloxWords attn_drop_words(uint32_t seed_lo, uint32_t seed_hi,
   return philox4x32_10(k, q4, bh, 0u, seed_lo, seed_hi);
 }
 
+// Token sampling (sampling.hip) draws from the same generator in a domain of
+// its own: counter = (v >> 2, row, step, 0x53414D50 "SAMP"), so c3 != 0 keeps
+// it apart from the dropout mask under one seed. The four words are those of
+// vocabulary entries v = 4*v4 .. 4*v4+3 of logits row `row` at token `step`.
+PHILOX_INL PhiloxWords sample_words(uint32_t seed_lo, uint32_t seed_hi,
+                                    uint32_t row, uint32_t step, uint32_t v4) {
+  return philox4x32_10(v4, row, step, 0x53414D50u, seed_lo, seed_hi);
+}
+
 // 4-bit keep mask of one call: bit i set iff element q = 4*q4 + i is kept.
 PHILOX_INL uint32_t attn_drop_keep4(uint32_t seed_lo, uint32_t seed_hi,
                                     uint32_t bh, uint32_t q4, uint32_t k,

@@ -1,5 +1,6 @@
 """The extension's interface in fp32 torch: one plain function (no autograd)
-per entry point in ``ops.BACKEND_API`` and ``ops.RAGGED_API``, taking the same positional arguments
+per entry point in ``ops.BACKEND_API``, ``ops.RAGGED_API`` and
+``ops.SAMPLING_API``, taking the same positional arguments
 as the ``_C`` binding of that name and returning as many results with the
 same shapes and dtypes. ``ops._backend`` hands out this module wherever the
 HIP extension does not run: on the CPU and under ``MIDGPT_FORCE_REF=1``.
@@ -222,6 +223,37 @@ def attn_decode_ragged(q, k_cache, v_cache, kv_lens_dev, kv_lens_host, num_split
     return torch.cat([attn_decode(q[b:b + 1], k_cache[b:b + 1], v_cache[b:b + 1],
                                   lens[b], num_splits)
                       for b in range(B)], dim=0)
+
+
+# Seeded token sampling (ops.SAMPLING_API): top-k + Gumbel-max, the
+# definition of csrc/sampling.hip in fp32 on the logits' device. The Philox
+# words come from the host mirror, so one (seed, step) gives one stream on
+# either backend; the tokens agree wherever the top two scores are further
+# apart than fp32 rounding.
+def sample_tokens(logits, inv_t, top_k, seed, step):
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise RuntimeError(f"sample_tokens: logits must be (B, V), got {tuple(logits.shape)}")
+    inv_t, top_k = float(inv_t), int(top_k)
+    if not (math.isfinite(inv_t) and inv_t > 0):
+        raise RuntimeError(f"sample_tokens: inv_t must be finite and > 0, got {inv_t}")
+    if top_k < 0:
+        raise RuntimeError(f"sample_tokens: top_k >= 0 required (0: all), got {top_k}")
+    B, V = logits.shape
+    words = ref.sample_words(B, V, seed, step)
+    m = torch.from_numpy((words >> 9).astype("int32"))
+    t = (2 * m + 1).to(torch.float32) * 2.0 ** -24   # exact: < 2^24
+    noise = -torch.log(-torch.log(t))
+    lf = logits.float()
+    score = lf * inv_t + noise.to(logits.device)
+    if 1 <= top_k < V:
+        kth = torch.topk(lf, top_k, dim=-1).values[:, -1:]
+        score = score.masked_fill(lf < kth, float("-inf"))
+    # lowest index of the maximal score, spelled out: argmax's tie order is
+    # not defined on the GPU
+    best = score.max(dim=-1, keepdim=True).values
+    idx = torch.arange(V, device=logits.device).expand(B, V)
+    tok = torch.where(score == best, idx, V).min(dim=-1).values
+    return tok.clamp_(max=V - 1)   # a NaN row (outside the contract) has no maximum
 
 
 # GELU (tanh approximation)

@@ -117,6 +117,53 @@ def attn_dropout_keep(seed: int, B: int, H: int, T: int, p: float) -> torch.Tens
     return torch.from_numpy(np.ascontiguousarray(keep)).view(B, H, T, T)
 
 
+SAMPLE_DOMAIN = 0x53414D50  # "SAMP": counter word c3 of the sampling stream
+
+
+def sample_words(B: int, V: int, seed: int, step: int) -> np.ndarray:
+    """Bit-exact host mirror of csrc/philox.h:sample_words: uint32 (B, V),
+    the word of vocabulary entry v of logits row b at token ``step``.
+    Key = 64-bit seed, counter = (v >> 2, b, step, SAMPLE_DOMAIN), entry v
+    takes word v & 3."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    step = int(step)
+    if not 0 <= step < 1 << 32:
+        raise ValueError(f"sample_words: step must be in [0, 2^32), got {step}")
+    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    n4 = (V + 3) // 4
+    shape = (B, n4)
+    c0 = np.broadcast_to(np.arange(n4, dtype=np.uint64)[None, :], shape)
+    c1 = np.broadcast_to(np.arange(B, dtype=np.uint64)[:, None], shape)
+    c2 = np.full(shape, step, dtype=np.uint64)
+    c3 = np.full(shape, SAMPLE_DOMAIN, dtype=np.uint64)
+    words = np.stack(_philox4x32_10(c0, c1, c2, c3, k0, k1), axis=2)  # (B,n4,4)
+    return np.ascontiguousarray(words.reshape(B, n4 * 4)[:, :V]).astype(np.uint32)
+
+
+def sample_scores(logits: torch.Tensor, inv_t: float, seed: int, step: int) -> np.ndarray:
+    """The sampling definition's scores in float64, (B, V):
+    ``logit * inv_t - log(-log(t))`` with ``t = (2 * (word >> 9) + 1) * 2^-24``
+    (23 bits, strictly inside (0, 1)). The token of row b is the lowest index
+    among its candidates (``sample_candidates``) of maximal score."""
+    B, V = logits.shape
+    w = sample_words(B, V, seed, step)
+    t = (2.0 * (w >> 9).astype(np.float64) + 1.0) * 2.0 ** -24
+    noise = -np.log(-np.log(t))
+    lf = logits.detach().double().cpu().numpy()
+    return lf * float(inv_t) + noise
+
+
+def sample_candidates(logits: torch.Tensor, top_k) -> np.ndarray:
+    """bool (B, V): every entry, or with 1 <= top_k < V those whose logit is
+    >= the row's k-th largest (entries tied with the k-th are all kept)."""
+    lf = logits.detach().double().cpu().numpy()
+    B, V = lf.shape
+    if top_k is None or top_k <= 0 or top_k >= V:
+        return np.ones((B, V), dtype=bool)
+    kth = np.sort(lf, axis=1)[:, V - int(top_k)][:, None]
+    return lf >= kth
+
+
 def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                      dropout_p: float = 0.0, training: bool = False,
                      keep: torch.Tensor | None = None) -> torch.Tensor:

@@ -18,6 +18,7 @@ import pickle
 
 import torch
 
+from midgpt_amd import ops
 from midgpt_amd.config import ExperimentConfig
 from midgpt_amd.generate import generate, generate_ragged
 from midgpt_amd.models.gpt import GPT
@@ -98,9 +99,9 @@ def main():
     model, encode, decode, config = load_model_and_tokenizer(args.ckpt_dir,
                                                              device)
 
-    gen = torch.Generator(device="cpu")
-    if args.seed is not None:
-        gen.manual_seed(args.seed)
+    # seeded sampling (ops.sample_tokens): one --seed, one text, on the CPU
+    # and on the GPU alike; without one a seed is drawn
+    seed = ops.draw_sample_seed() if args.seed is None else args.seed
     starts = list(args.start or [])
     if args.start_file is not None:
         with open(args.start_file) as f:
@@ -110,7 +111,7 @@ def main():
                    for s in starts]
         outs = generate_ragged(model, prompts, args.max_new_tokens,
                                temperature=args.temperature, top_k=args.top_k,
-                               eos_id=args.eos_id, generator=gen)
+                               eos_id=args.eos_id, seed=seed)
         for o in outs:
             print(decode(o.tolist()))
             print("---------------")
@@ -119,7 +120,7 @@ def main():
     prompt = torch.tensor(encode(start), dtype=torch.int64, device=device)
     prompt = prompt.unsqueeze(0).expand(args.num_samples, -1)
     out = generate(model, prompt, args.max_new_tokens,
-                   temperature=args.temperature, generator=gen)
+                   temperature=args.temperature, seed=seed)
     for i in range(args.num_samples):
         print(decode(out[i].tolist()))
         print("---------------")

@@ -26,6 +26,18 @@
                     environment selects and nothing else: run it under
                     ``rocprofv3 --kernel-trace --stats`` at two values of
                     --new; the difference in dispatches is launches per token.
+                    Greedy, or with --sampled at temperature 0.8, top_k 50,
+                    seed= (the sample_tokens kernel).
+  --which sampling  the last step of a token. Kernel: ops.sample_tokens at
+                    B = 1, 8, 64, V = 50304, top_k none and 50, against
+                    generate._sample (the torch chain) on the same logits with
+                    the device multinomial and with a CPU generator (the
+                    probability matrix copied to the host), the three
+                    alternating over a ring of 4 logit tensors: hot in cache,
+                    as the lm_head has just written them in a real step. End
+                    to end: the --which ragged set-up at temperature 0.8,
+                    top_k 50 with seed=, the same with a CPU generator, and
+                    greedy, alternating.
 """
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -209,6 +221,72 @@ def bench_ragged_e2e(reps, n_new=128):
           flush=True)
 
 
+def bench_sample_kernel(B, V, top_k):
+    from midgpt_amd.generate import _sample
+    ring = [(4.0 * torch.randn(B, V, device=DEV)).to(BF) for _ in range(4)]
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    step = [0]
+
+    def seeded(lg):
+        step[0] += 1
+        return ops.sample_tokens(lg, 0.8, top_k, seed=1, step=step[0])
+
+    paths = {
+        "sample_tokens (seed=)": [(lambda lg=lg: seeded(lg)) for lg in ring],
+        "_sample device multinomial": [(lambda lg=lg: _sample(lg, 0.8, top_k, None))
+                                       for lg in ring],
+        "_sample CPU generator": [(lambda lg=lg: _sample(lg, 0.8, top_k, gen))
+                                  for lg in ring],
+    }
+    res = {name: [] for name in paths}
+    for _ in range(3):                                    # alternating
+        for name, fns in paths.items():
+            res[name].append(time_ring(fns, 200) * 1e6)
+    for name, r in res.items():
+        print(f"sampling B{B} V{V} top_k {top_k}: {name:27s} "
+              f"{statistics.median(r):9.1f} us (min {min(r):.1f} max {max(r):.1f})",
+              flush=True)
+
+
+def bench_sample_e2e(reps, n_new=128):
+    from midgpt_amd.generate import generate_ragged
+    model, cfg = xl_model()
+    lens = [16, 48, 96, 160, 240, 320, 416, 512]
+    g = torch.Generator().manual_seed(0)
+    prompts = [torch.randint(0, cfg.vocab_size, (n,), generator=g).to(DEV) for n in lens]
+    print(f"sampling e2e: openwebtext_xl, generate_ragged, prompts {lens}, {n_new} new "
+          "tokens each; time includes the prompts", flush=True)
+    paths = {
+        "T=0.8 top_k=50 seed=": lambda n: generate_ragged(
+            model, prompts, n, temperature=0.8, top_k=50, seed=1),
+        "T=0.8 top_k=50 CPU generator": lambda n: generate_ragged(
+            model, prompts, n, temperature=0.8, top_k=50,
+            generator=torch.Generator(device="cpu").manual_seed(1)),
+        "greedy": lambda n: generate_ragged(model, prompts, n, temperature=0.0),
+    }
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        outs = fn(n_new)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        assert [o.numel() for o in outs] == [m + n_new for m in lens]
+        return dt
+
+    for fn in paths.values():                             # warm up all
+        fn(8)
+    res = {name: [] for name in paths}
+    for _ in range(reps):                                 # alternating
+        for name, fn in paths.items():
+            res[name].append(timed(fn))
+    for name, ts in res.items():
+        tps = sorted(len(lens) * n_new / t for t in ts)
+        print(f"sampling e2e {name:29s}: tokens/s median {statistics.median(tps):8.1f} "
+              f"min {tps[0]:8.1f} max {tps[-1]:8.1f}  (wall median "
+              f"{statistics.median(ts)*1e3:8.1f} ms) over {reps} runs", flush=True)
+
+
 def xl_model():
     from midgpt_amd.config import load_config
     from midgpt_amd.models.gpt import GPT
@@ -262,21 +340,25 @@ def bench_e2e(reps, n_prompt=128, n_new=256):
               flush=True)
 
 
-def run_count(n_new):
+def run_count(n_new, sampled):
     model, cfg = xl_model()
     idx = torch.randint(0, cfg.vocab_size, (1, 128), device=DEV)
     from midgpt_amd.generate import generate, native_decode
-    print(f"count: native={native_decode(model)} new={n_new}", flush=True)
-    generate(model, idx, n_new, temperature=0.0)
+    print(f"count: native={native_decode(model)} new={n_new} sampled={sampled}", flush=True)
+    if sampled:
+        generate(model, idx, n_new, temperature=0.8, top_k=50, seed=1)
+    else:
+        generate(model, idx, n_new, temperature=0.0)
     torch.cuda.synchronize()
 
 
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
-    p.add_argument("--which", default="all", choices=["all", "kernels", "ragged", "e2e", "count"])
+    p.add_argument("--which", default="all", choices=["all", "kernels", "ragged", "e2e", "count", "sampling"])
     p.add_argument("--sweep", action="store_true")
     p.add_argument("--reps", type=int, default=3)
     p.add_argument("--new", type=int, default=32)
+    p.add_argument("--sampled", action="store_true")
     args = p.parse_args()
     if args.which in ("all", "kernels"):
         for B in (1, 8, 64):
@@ -297,5 +379,10 @@ if __name__ == "__main__":
         bench_ragged_e2e(max(3, args.reps))
     if args.which in ("all", "e2e"):
         bench_e2e(max(3, args.reps))
+    if args.which in ("all", "sampling"):
+        for B in (1, 8, 64):
+            for top_k in (None, 50):
+                bench_sample_kernel(B, 50304, top_k)
+        bench_sample_e2e(max(3, args.reps))
     if args.which == "count":
-        run_count(args.new)
+        run_count(args.new, args.sampled)

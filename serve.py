@@ -9,7 +9,8 @@ same way sample.py does, then serves batched KV-cache generation
     python serve.py --ckpt_dir runs/xl [--host 127.0.0.1 --port 8000]
 
     POST /generate {"prompt": "...", "max_new_tokens": 200,
-                    "temperature": 0.8, "num_samples": 1}
+                    "temperature": 0.8, "top_k": null, "num_samples": 1,
+                    "seed": null}
     POST /generate_batch {"prompts": ["...", "..."], "max_new_tokens": 200,
                           "temperature": 0.8, "top_k": null, "seed": null,
                           "eos_id": null}
@@ -17,12 +18,22 @@ same way sample.py does, then serves batched KV-cache generation
          prompt, each at most block_size tokens long with its prompt (no
          sliding window), cut after its first eos_id if that is given
     GET  /healthz
+
+Sampling is seeded (``ops.sample_tokens``): "seed" fixes the text of a
+request, on the CPU and on the GPU alike; without one a seed is drawn from
+torch's CPU generator.
 """
 import argparse
 
 import torch
 
 from sample import load_model_and_tokenizer
+
+
+def _seed_of(seed):
+    """The request's seed, or a fresh one: sampling stays on the device."""
+    from midgpt_amd import ops
+    return ops.draw_sample_seed() if seed is None else seed
 
 
 def build_app(ckpt_dir: str, device: str | None = None):
@@ -37,6 +48,7 @@ def build_app(ckpt_dir: str, device: str | None = None):
         prompt: str = "\n"
         max_new_tokens: int = 200
         temperature: float = 0.8
+        top_k: int | None = None
         num_samples: int = 1
         seed: int | None = None
 
@@ -61,11 +73,9 @@ def build_app(ckpt_dir: str, device: str | None = None):
         ids = encode(req.prompt)
         idx = torch.tensor([ids] * req.num_samples, dtype=torch.long,
                            device=device)
-        gen = None
-        if req.seed is not None:
-            gen = torch.Generator().manual_seed(req.seed)
         out = generate(model, idx, req.max_new_tokens,
-                       temperature=req.temperature, generator=gen)
+                       temperature=req.temperature, top_k=req.top_k,
+                       seed=_seed_of(req.seed))
         return {"samples": [decode(out[i].tolist())
                             for i in range(req.num_samples)]}
 
@@ -77,12 +87,9 @@ def build_app(ckpt_dir: str, device: str | None = None):
                    for p in req.prompts]
         if any(p.numel() == 0 for p in prompts):
             raise HTTPException(status_code=422, detail="empty prompt")
-        gen = None
-        if req.seed is not None:
-            gen = torch.Generator().manual_seed(req.seed)
         outs = generate_ragged(model, prompts, req.max_new_tokens,
                                temperature=req.temperature, top_k=req.top_k,
-                               eos_id=req.eos_id, generator=gen)
+                               eos_id=req.eos_id, seed=_seed_of(req.seed))
         return {"samples": [decode(o.tolist()) for o in outs]}
 
     return app

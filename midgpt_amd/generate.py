@@ -22,9 +22,16 @@ step per token (``prefill_ragged`` + ``decode_step_ragged`` on
 lengths in the ``KVCache``, every sequence advancing by the same number of
 tokens per step. It has no sliding window (a sequence whose cache is full is
 finished) and does not compact the batch when sequences finish.
+
+``DecodeScheduler`` / ``generate_continuous`` do: the ``KVCache`` is a pool of
+slots, a step runs the rows named by a slot map (``decode_step_slots`` on
+``ops.kv_append_slots`` / ``ops.decode_attention_slots``), requests join and
+leave between steps, and every request samples with its own parameters
+(``ops.sample_tokens_rows``), so its text does not depend on its batch.
 """
 from __future__ import annotations
 
+import collections
 import math
 import os
 
@@ -278,6 +285,30 @@ def _native_cache(cache: KVCache) -> bool:
     return cache.buf.is_cuda and cache.buf.dtype == torch.bfloat16
 
 
+def _prefill_attend(model, cache: KVCache, ks, vs, B, Lmax):
+    """``attend`` of ``_ragged_layers`` for B prompts run from position 0 into
+    the per-layer caches ``ks`` / ``vs`` (B,H,block_size,C): ``cache``'s own
+    views, or one slot of them."""
+    sin, cos = model.rope_sin, model.rope_cos
+    if _native_cache(cache) or not cache.buf.is_cuda:
+        def attend(li, qkv):
+            qw, kw = cache.ln_w[li]
+            return _attend_cached(qkv, qw, kw, sin, cos, ks[li], vs[li], 0)
+    else:
+        # ref_backend on the GPU (fp32 caches): the uniform ops would pick the
+        # kernels there, so the 16-row chunks go through the ragged pair
+        def attend(li, qkv):
+            qw, kw = cache.ln_w[li]
+            outs = []
+            for s in range(0, Lmax, 16):
+                chunk = qkv[:, s:s + 16]
+                q = ops.kv_append_ragged(chunk, qw, kw, sin, cos, ks[li], vs[li], [s] * B)
+                outs.append(ops.decode_attention_ragged(
+                    q, ks[li], vs[li], [s + chunk.shape[1]] * B))
+            return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+    return attend
+
+
 @torch.no_grad()
 def prefill_ragged(model, prompts, cache: KVCache) -> torch.Tensor:
     """Start a batch of prompts of different lengths: ``prompts`` is a list of
@@ -300,28 +331,9 @@ def prefill_ragged(model, prompts, cache: KVCache) -> torch.Tensor:
     for b, p in enumerate(prompts):
         idx[b, :lens[b]] = p
     idx = idx.to(dev)
-    sin, cos = model.rope_sin, model.rope_cos
     cache.set_lens([0] * B)
-
-    if _native_cache(cache) or not cache.buf.is_cuda:
-        def attend(li, qkv):
-            qw, kw = cache.ln_w[li]
-            return _attend_cached(qkv, qw, kw, sin, cos, cache.k[li], cache.v[li], 0)
-    else:
-        # ref_backend on the GPU (fp32 caches): the uniform ops would pick the
-        # kernels there, so the 16-row chunks go through the ragged pair
-        def attend(li, qkv):
-            qw, kw = cache.ln_w[li]
-            outs = []
-            for s in range(0, Lmax, 16):
-                chunk = qkv[:, s:s + 16]
-                q = ops.kv_append_ragged(chunk, qw, kw, sin, cos, cache.k[li],
-                                         cache.v[li], [s] * B)
-                outs.append(ops.decode_attention_ragged(
-                    q, cache.k[li], cache.v[li], [s + chunk.shape[1]] * B))
-            return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
-
-    x, pending = _ragged_layers(model, idx, attend)
+    x, pending = _ragged_layers(model, idx,
+                                _prefill_attend(model, cache, cache.k, cache.v, B, Lmax))
     last = torch.tensor(lens, device=dev) - 1
     rows = torch.arange(B, device=dev)
     x = x[rows, last][:, None]
@@ -436,6 +448,284 @@ def generate_ragged(model, prompts, max_new_tokens: int, temperature: float = 1.
                 new = new[:int(hit[0]) + 1]
         out.append(torch.cat([p, new.to(p.device)]))
     return out
+
+
+@torch.no_grad()
+def decode_step_slots(model, idx_new: torch.Tensor, cache: KVCache, slots,
+                      slots_dev=None) -> torch.Tensor:
+    """``decode_step_ragged`` for the rows named by ``slots`` in a pool
+    ``cache`` of S >= B slots: idx_new (B, Tn), Tn <= 16, with row b at
+    positions cache.lens[slots[b]] .. +Tn-1 of slot slots[b]; returns the last
+    position's logits (B, V). ``slots`` is B distinct host integers;
+    ``slots_dev`` their int32 device copy (uploaded here when absent).
+
+    The per-slot lengths ``cache.lens`` / ``cache.lens_dev`` are indexed by
+    slot and advance for the named slots only, by the retire-when-full rule of
+    ``decode_step_ragged``, on the device without upload or sync (a gather, a
+    clamp, an add and a scatter per step, however many layers read them)."""
+    B, Tn = idx_new.shape
+    block = cache.block_size
+    slots = [int(s) for s in slots]
+    S = len(cache.lens)
+    if not 1 <= Tn <= 16:
+        raise RuntimeError(f"decode_step_slots: 1 <= Tn <= 16 required, got {Tn}")
+    if len(slots) != B or len(set(slots)) != B or not all(0 <= s < S for s in slots):
+        raise RuntimeError(f"decode_step_slots: {B} distinct slots in [0, {S}) "
+                           f"expected, got {slots}")
+    lens = [cache.lens[s] for s in slots]
+    for n in lens:
+        if n < block and n + Tn > block:
+            raise RuntimeError(f"decode_step_slots: positions [{n}, {n + Tn}) "
+                               f"exceed block_size {block}")
+    if slots_dev is None:
+        slots_dev = torch.tensor(slots, dtype=torch.int32, device=cache.lens_dev.device)
+    pos = [min(n, block - Tn) for n in lens]
+    kv_lens = [p + Tn for p in pos]
+    pos_dev = cache.lens_dev[slots_dev].clamp(max=block - Tn)
+    kv_lens_dev = pos_dev + Tn
+    sin, cos = model.rope_sin, model.rope_cos
+
+    def attend(li, qkv):
+        qw, kw = cache.ln_w[li]
+        q = ops.kv_append_slots(qkv, qw, kw, sin, cos, cache.k[li], cache.v[li],
+                                pos, slots, pos_dev, slots_dev)
+        return ops.decode_attention_slots(q, cache.k[li], cache.v[li], kv_lens, slots,
+                                          kv_lens_dev, slots_dev)
+
+    x, pending = _ragged_layers(model, idx_new, attend)
+    for s, n in zip(slots, kv_lens):
+        cache.lens[s] = n
+    cache.lens_dev[slots_dev] = kv_lens_dev
+    return _ragged_logits(model, x[:, -1:],
+                          None if pending is None else pending[:, -1:])
+
+
+class Request:
+    """Handle of one ``DecodeScheduler.submit``: ``done`` once the request has
+    left the scheduler, and then ``tokens`` = the prompt plus what it
+    generated (1-D int64, on the prompt's device)."""
+
+    def __init__(self, prompt, budget, temperature, top_k, seed, row, eos_id):
+        self.prompt = prompt
+        self.budget = budget
+        self.temperature = float(temperature)
+        self.top_k = top_k
+        self.seed = seed
+        self.row = int(row)
+        self.eos_id = eos_id
+        self.done = False
+        self.tokens = None
+        self._new = []        # generated tokens the host has seen
+        self._drawn = 0       # tokens sampled on the device so far
+        self._slot = None
+
+    def _finish(self):
+        new = torch.tensor(self._new, dtype=torch.int64)
+        self.tokens = torch.cat([self.prompt, new.to(self.prompt.device)])
+        self.done = True
+
+
+class DecodeScheduler:
+    """Continuous batching over a pool of ``num_slots`` full-length caches:
+    requests are queued by ``submit``, admitted into free slots, decoded
+    together one token per ``step`` and retired as they finish, while the
+    others go on. Synchronous, no threads: the caller drives ``step`` (or
+    ``run``).
+
+    Every ``tick_every`` steps (and at once when nothing is active and the
+    queue is not empty, or when every active row has spent its budget) a step
+    ends with a tick: one device-to-host copy of the tokens drawn since the
+    last one; rows that hit their ``eos_id`` or spent their budget are retired,
+    their surplus tokens dropped as in ``generate_ragged``, and their slots
+    freed; queued requests are admitted into free slots in FIFO order, each
+    prompt prefilled alone at B=1 into its slot and its first token drawn at
+    step 0 with its own parameters; then the slot map, the per-slot lengths
+    and the per-row sampling parameters go to the device in one upload.
+    Between ticks the active set is fixed, finished rows keep stepping (as
+    retired rows do in ``decode_step_ragged``), nothing is uploaded and nothing
+    syncs. ``tick_every`` is a parameter, not a measured optimum: a small value
+    frees slots sooner, a large one syncs less often.
+
+    Token t of a request is drawn by ``ops.sample_tokens_rows`` with the
+    request's own (seed, step=t, row), whatever else shares the step: a
+    request with (seed=s, row=r) reproduces row r of ``generate(..., seed=s)``
+    wherever the logits agree. temperature <= 0 is greedy.
+
+    Limits: no paging (a slot is a whole block_size cache) and no sliding
+    window (budget = min(max_new_tokens, block_size - L + 1) as in
+    ``generate_ragged``); admitted prompts are prefilled one at a time, not as
+    a batch, and a prefill is not interleaved with decode steps.
+
+    Native under ``native_decode(model)``; otherwise the same code runs on
+    ``ops.ref_backend`` with fp32 caches."""
+
+    def __init__(self, model, num_slots: int, tick_every: int = 8):
+        if num_slots < 1 or tick_every < 1:
+            raise ValueError("DecodeScheduler: num_slots >= 1 and tick_every >= 1 required")
+        model.eval()
+        self.model = model
+        self.tick_every = int(tick_every)
+        self.cache = KVCache(model, num_slots,
+                             dtype=None if native_decode(model) else torch.float32)
+        self.queue = collections.deque()
+        self.free = list(range(num_slots))
+        self.active = []          # requests, in batch-row order
+        self._finished = []       # retired since the last step() returned
+        self._since_tick = 0
+        self._nxt = None          # (B,) last token of every active row, on the device
+        self._cols = []           # (B,) token columns since the last tick
+        self._fresh = []          # per active row: column 0 has not been read yet
+        self._slots_dev = self._params_dev = None
+
+    def submit(self, prompt, max_new_tokens: int, temperature: float = 1.0,
+               top_k: int | None = None, seed: int | None = None, row: int = 0,
+               eos_id: int | None = None) -> Request:
+        """Queue a request; returns its handle. The prompt (1-D int64, at least
+        one token) conditions on its last block_size tokens. Without ``seed``
+        one is drawn by ``ops.draw_sample_seed``."""
+        block = self.cache.block_size
+        prompt = prompt.reshape(-1)
+        if prompt.numel() < 1:
+            raise RuntimeError("DecodeScheduler.submit: empty prompt")
+        L = min(int(prompt.numel()), block)
+        budget = max(0, min(int(max_new_tokens), block - L + 1))
+        if seed is None:
+            seed = ops.draw_sample_seed()
+        req = Request(prompt, budget, temperature, top_k, seed, row, eos_id)
+        # validates the sampling parameters now, not at admission
+        ops.sample_row_params(req.temperature, top_k, [seed], [0], [req.row], 1)
+        if budget == 0:
+            req._finish()
+            self._finished.append(req)
+        else:
+            self.queue.append(req)
+        return req
+
+    def pending(self) -> bool:
+        """Whether a request is queued or active."""
+        return bool(self.queue or self.active)
+
+    @torch.no_grad()
+    def step(self) -> list:
+        """One decode step for the active rows, with a tick where one is due;
+        returns the handles that finished."""
+        if not self.active and self.queue:
+            self._tick()
+        if self.active:
+            slots = [r._slot for r in self.active]
+            logits = decode_step_slots(self.model, self._nxt[:, None], self.cache, slots,
+                                       self._slots_dev)
+            self._draw(logits)
+            self._since_tick += 1
+            if self._since_tick >= self.tick_every or \
+                    all(r._drawn >= r.budget for r in self.active):
+                self._tick()
+        done, self._finished = self._finished, []
+        return done
+
+    def run(self) -> list:
+        """Step until queue and pool are empty; returns the finished handles."""
+        done = []
+        while True:
+            done += self.step()
+            if not self.pending():
+                return done
+
+    def _draw(self, logits):
+        act = self.active
+        self._nxt = ops.sample_tokens_rows(
+            logits, [r.temperature for r in act], [r.top_k for r in act],
+            seeds=[r.seed for r in act], steps=[r._drawn for r in act],
+            rows=[r.row for r in act], params_dev=self._params_dev)
+        self._cols.append(self._nxt)
+        self._params_dev[:, 2] += 1   # the step column, as on the host
+        for r in act:
+            r._drawn += 1
+
+    def _admit(self, req, slot):
+        """Prefill the prompt alone into its slot; its first token, on the
+        device, drawn at step 0 with its own parameters."""
+        model, cache = self.model, self.cache
+        idx = req.prompt[-cache.block_size:][None].to(model.wte.device)
+        L = idx.shape[1]
+        ks = [k[slot:slot + 1] for k in cache.k]
+        vs = [v[slot:slot + 1] for v in cache.v]
+        x, pending = _ragged_layers(model, idx, _prefill_attend(model, cache, ks, vs, 1, L))
+        logits = _ragged_logits(model, x[:, -1:],
+                                None if pending is None else pending[:, -1:])
+        req._slot = slot
+        req._drawn = 1
+        cache.lens[slot] = L
+        return ops.sample_tokens_rows(logits, req.temperature, [req.top_k],
+                                      seeds=[req.seed], steps=[0], rows=[req.row])
+
+    def _tick(self):
+        dev = self.model.wte.device
+        keep = []                 # index into the old rows of those that stay
+        if self.active:
+            toks = torch.stack(self._cols, dim=1).cpu()   # the one copy of a tick
+            for b, req in enumerate(self.active):
+                for tok in toks[b, 0 if self._fresh[b] else 1:].tolist():
+                    if len(req._new) == req.budget:
+                        break
+                    req._new.append(tok)
+                    if tok == req.eos_id:
+                        break
+                if len(req._new) == req.budget or req._new[-1:] == [req.eos_id]:
+                    req._finish()
+                    self.free.append(req._slot)
+                    self._finished.append(req)
+                else:
+                    keep.append(b)
+        stay = [self.active[b] for b in keep]
+        firsts = []
+        self.free.sort()
+        while self.queue and self.free:
+            req = self.queue.popleft()
+            firsts.append(self._admit(req, self.free.pop(0)))
+            stay.append(req)
+        n_old = len(self.active)
+        self._fresh = [False] * len(keep) + [True] * len(firsts)
+        self.active = stay
+        self._since_tick = 0
+        if not stay:
+            self._nxt, self._cols = None, []
+            return
+        # one upload: per-slot lengths | slot map | rows kept | sampling parameters
+        S, B = len(self.cache.lens), len(stay)
+        host = ops.sample_row_params(
+            [r.temperature for r in stay], [r.top_k for r in stay], [r.seed for r in stay],
+            [r._drawn for r in stay], [r.row for r in stay], B)
+        meta = torch.tensor(self.cache.lens + [r._slot for r in stay]
+                            + keep + list(range(n_old, n_old + len(firsts))),
+                            dtype=torch.int32)
+        buf = torch.cat([meta, ops.pack_sample_params(*host).reshape(-1)]).to(dev)
+        self.cache.lens_dev = buf[:S]
+        self._slots_dev = buf[S:S + B]
+        self._params_dev = buf[S + 2 * B:].view(B, 6)
+        src = torch.cat(([self._nxt] if n_old else []) + firsts)
+        self._nxt = src[buf[S + B:S + 2 * B]]
+        self._cols = [self._nxt]
+
+
+@torch.no_grad()
+def generate_continuous(model, prompts, max_new_tokens: int, temperature: float = 1.0,
+                        top_k: int | None = None, eos_id: int | None = None,
+                        num_slots: int = 8, tick_every: int = 8,
+                        seed: int | None = None) -> list:
+    """``generate_ragged`` on a ``DecodeScheduler`` of ``num_slots`` slots:
+    every prompt is submitted (prompt i with ``row=i`` and the one ``seed``,
+    drawn when None), the scheduler runs until all are done, and the results
+    come back in order. There may be more prompts than slots: the rest wait
+    for a slot. With a seed, prompt i gets the tokens row i of
+    ``generate(..., seed=seed)`` gets wherever the logits agree."""
+    if seed is None:
+        seed = ops.draw_sample_seed()
+    sched = DecodeScheduler(model, num_slots, tick_every)
+    handles = [sched.submit(p, max_new_tokens, temperature, top_k, seed=seed, row=i,
+                            eos_id=eos_id) for i, p in enumerate(prompts)]
+    sched.run()
+    return [h.tokens for h in handles]
 
 
 def _check_seed(seed, generator):

@@ -33,6 +33,9 @@ BACKEND_API = (
 RAGGED_API = ("kv_append_ragged", "attn_decode_ragged")
 # Seeded token sampling, under the same rule.
 SAMPLING_API = ("sample_tokens",)
+# Slot-mapped decode and per-row sampling (continuous batching), under the
+# same rule.
+SLOT_API = ("kv_append_slots", "attn_decode_slots", "sample_tokens_rows")
 
 
 def _try_load_ext():
@@ -420,6 +423,63 @@ def decode_attention_ragged(q, k_cache, v_cache, kv_lens, kv_lens_dev=None,
         kv_lens, int(num_splits)).view(B, Tq, H * C)
 
 
+# Slotted decode: the caches are a pool (S,H,Tmax,C) of S >= B slots and batch
+# row b lives in slot slots[b], so a batch can change from step to step
+# without moving a cache. ``slots`` (host: Python ints or a CPU integer
+# tensor) is B distinct slots in [0, S) and is validated like the positions;
+# ``slots_dev`` is the optional int32 GPU copy, under the same contract as
+# ``pos_dev``. Row b has the bits of the ragged op on the gathered cache[slots].
+def _host_slots(slots, B, S, who):
+    slots = _host_lens(slots, B, who)
+    vals = slots.tolist()
+    if S < B or not all(0 <= s < S for s in vals):
+        raise RuntimeError(f"{who}: {B} slots in [0, {S}) expected, got {vals}")
+    if len(set(vals)) != B:
+        raise RuntimeError(f"{who}: a slot is named twice in {vals} (two rows "
+                           "would race on one cache)")
+    return slots
+
+
+def kv_append_slots(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
+                    pos, slots, pos_dev=None, slots_dev=None, eps: float = 1e-6):
+    """``kv_append_ragged`` into a pool: qkv (B,Tn,3,H,C), caches
+    (S,H,Tmax,C) with S >= B. Writes rows [pos[b], pos[b]+Tn) of slot slots[b]
+    and nothing else; returns q (B,H,Tn,C)."""
+    who = "kv_append_slots"
+    B, Tn = qkv.shape[:2]
+    pos = _host_lens(pos, B, who)
+    if k_cache.dim() != 4:
+        raise RuntimeError(f"{who}: the caches must be (S,H,Tmax,C)")
+    slots = _host_slots(slots, B, k_cache.shape[0], who)
+    for p in pos.tolist():
+        _check_append(qkv, sin, cos, k_cache[:B], v_cache[:B], p)
+    return _ragged_backend(qkv, k_cache).kv_append_slots(
+        qkv.contiguous(), q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
+        _dev_lens(pos, pos_dev, qkv), pos, _dev_lens(slots, slots_dev, qkv), slots, eps)
+
+
+def decode_attention_slots(q, k_cache, v_cache, kv_lens, slots, kv_lens_dev=None,
+                           slots_dev=None, num_splits: int = 0):
+    """``decode_attention_ragged`` on a pool: sequence b holds kv_lens[b]
+    positions in slot slots[b] of the caches (S,H,Tmax,C). Returns o
+    (B,Tq,H*C). ``num_splits`` = 0 applies the uniform rule to the longest
+    sequence, as the ragged op does."""
+    who = "decode_attention_slots"
+    B, H, Tq, C = q.shape
+    kv_lens = _host_lens(kv_lens, B, who)
+    if k_cache.dim() != 4:
+        raise RuntimeError(f"{who}: the caches must be (S,H,Tmax,C)")
+    slots = _host_slots(slots, B, k_cache.shape[0], who)
+    Tmax = k_cache.shape[2]
+    for n in kv_lens.tolist():
+        if n > Tmax or not 1 <= Tq <= min(16, n):
+            raise RuntimeError(f"{who}: Tq {Tq} <= kv_len {n} <= "
+                               f"{Tmax} (the cache) required, Tq <= 16")
+    return _ragged_backend(q, k_cache).attn_decode_slots(
+        q.contiguous(), k_cache, v_cache, _dev_lens(kv_lens, kv_lens_dev, q), kv_lens,
+        _dev_lens(slots, slots_dev, q), slots, int(num_splits)).view(B, Tq, H * C)
+
+
 def prefill_attention(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
                       eps: float = 1e-6):
     """A whole prompt at position 0: qkv (B,Tn,3,H,C) -> o (B,Tn,H*C), with
@@ -493,6 +553,82 @@ def sample_tokens(logits, temperature: float, top_k: int | None = None, *,
     if logits.dtype != torch.bfloat16 or not logits.is_contiguous():
         impl = ref_backend
     return impl.sample_tokens(logits, inv_t, top_k, _seed_i64(seed), step)
+
+
+def sample_row_params(temperature, top_k, seeds, steps, rows, B: int):
+    """The per-row arguments of ``sample_tokens_rows`` as the five validated
+    host tensors a backend takes: (inv_t float32, top_k, seeds, steps, rows
+    int64), each (B,). ``temperature`` and ``top_k`` may be one value for every
+    row; temperature <= 0 marks a greedy row (inv_t 0); top_k None or 0: all."""
+    def seq(x, name):
+        x = list(x) if hasattr(x, "__len__") else [x] * B
+        if len(x) != B:
+            raise RuntimeError(f"sample_tokens_rows: {B} values of {name} expected, "
+                               f"got {len(x)}")
+        return x
+    inv_t = []
+    for t in seq(temperature, "temperature"):
+        t, it = float(t), 0.0
+        if t > 0.0:
+            # fp32(1/T), computed once, is what every backend multiplies by
+            it = torch.tensor(1.0 / t, dtype=torch.float32).item()
+            if not (math.isfinite(it) and it > 0.0):
+                raise RuntimeError(f"sample_tokens_rows: 1/temperature is {it} in fp32")
+        inv_t.append(it)
+    ks = [0 if k is None else int(k) for k in seq(top_k, "top_k")]
+    if min(ks, default=0) < 0:
+        raise RuntimeError(f"sample_tokens_rows: top_k must be >= 0, got {ks}")
+    seeds = [_seed_i64(x) for x in seq(seeds, "seeds")]
+    steps = [int(x) for x in seq(steps, "steps")]
+    rows = [int(x) for x in seq(rows, "rows")]
+    for name, vals in (("step", steps), ("row", rows)):
+        if not all(0 <= x < 1 << 32 for x in vals):
+            raise RuntimeError(f"sample_tokens_rows: {name} must be in [0, 2^32), got {vals}")
+    i64 = lambda x: torch.tensor(x, dtype=torch.int64)
+    return (torch.tensor(inv_t, dtype=torch.float32), i64(ks), i64(seeds), i64(steps),
+            i64(rows))
+
+
+def pack_sample_params(inv_t, top_k, seeds, steps, rows, device=None):
+    """What the kernel reads of ``sample_row_params``' tensors: (B, 6) int32,
+    row b = {seed low word, seed high word, step, row, bits of fp32 inv_t,
+    top_k clamped to int32} (csrc/sampling.hip). Column 2 is the step: a
+    caller that keeps the tensor advances it there."""
+    # the low 32 bits of an int64 as the int32 of the same bit pattern
+    u32 = lambda x: ((x & 0xFFFFFFFF) - ((x & 0x80000000) << 1)).to(torch.int32)
+    p = torch.stack([u32(seeds), u32(seeds >> 32), u32(steps), u32(rows),
+                     inv_t.view(torch.int32),
+                     top_k.clamp(max=2 ** 31 - 1).to(torch.int32)], dim=1).contiguous()
+    return p if device is None else p.to(device)
+
+
+def sample_tokens_rows(logits, temperature, top_k=None, *, seeds, steps, rows,
+                       params_dev=None):
+    """``sample_tokens`` with per-row parameters: logits (B, V) -> tokens (B,)
+    int64, row b drawn with its own temperature[b], top_k[b], seeds[b] and
+    steps[b], and with rows[b] as the Philox counter word that
+    ``sample_tokens`` fills with the batch index. So
+    ``out[b] == sample_tokens(X, T_b, k_b, seed=s_b, step=t_b)[r_b]`` for any X
+    whose row r_b is logits[b]: what a request draws does not depend on who
+    shares its batch. The per-row arguments are host sequences of length B
+    (temperature and top_k may be one value); they are the truth and are
+    validated. A row with temperature <= 0 is greedy: the lowest index of the
+    largest logit, ``top_k`` ignored.
+
+    ``params_dev``: the optional GPU copy, ``pack_sample_params(...)``, which a
+    caller uploads once and keeps equal to the host values (advancing the step
+    column on the device). Contiguous bf16 logits on the GPU run
+    csrc/sampling.hip; everything else goes to ref_backend."""
+    if logits.dim() != 2:
+        raise ValueError(f"sample_tokens_rows: logits must be (B, V), got {tuple(logits.shape)}")
+    B = logits.shape[0]
+    host = sample_row_params(temperature, top_k, seeds, steps, rows, B)
+    impl = _backend(logits)
+    if logits.dtype != torch.bfloat16 or not logits.is_contiguous():
+        impl = ref_backend
+    if params_dev is None:
+        params_dev = pack_sample_params(*host, device=logits.device)
+    return impl.sample_tokens_rows(logits, params_dev, *host)
 
 
 def draw_sample_seed() -> int:

@@ -688,13 +688,18 @@ torch::Tensor gelu_bwd(torch::Tensor dy, torch::Tensor x) {
 
 // ---------------------------------------------------------------------------
 // KV-cache decode (decode.hip). Caches are (B,H,Tmax,C) bf16, contiguous;
-// returns Tmax.
+// returns Tmax. pool: the caches are a pool of S >= B slots, (S,H,Tmax,C),
+// and *pool receives S.
 static int64_t decode_caches(const Call& c, const torch::Tensor& k_cache,
                              const torch::Tensor& v_cache, int B, int H, int C, u16** kp,
-                             u16** vp) {
+                             u16** vp, int* pool = nullptr) {
   TORCH_CHECK(C == 64 || C == 128, c.who, ": head dim 64 or 128 (got ", C, ")");
-  *kp = c.bf16_out(k_cache, "k_cache", {B, H, ANY, C});
+  *kp = c.bf16_out(k_cache, "k_cache", {pool ? ANY : B, H, ANY, C});
   *vp = c.bf16_out(v_cache, "v_cache", k_cache.sizes());
+  if (pool) {
+    *pool = c.dim(k_cache, 0);
+    TORCH_CHECK(*pool >= B, c.who, ": a pool of ", *pool, " slots cannot hold ", B, " rows");
+  }
   return k_cache.size(2);
 }
 
@@ -710,18 +715,50 @@ static std::vector<int64_t> host_lens(const torch::Tensor& t, int B, const char*
   return std::vector<int64_t>(p, p + B);
 }
 
+// The slot map of a slotted call: batch row b lives in cache slot slots[b].
+// Host copy (the truth, validated here: B distinct slots in [0, S); two rows
+// in one slot would race on its cache) and the (B,) int32 device copy that
+// the kernels read, which the caller keeps equal to it.
+struct SlotMap {
+  std::vector<int64_t> host;
+  const int* dev = nullptr;  // null: not a slotted call
+  int S = 0;
+};
+static SlotMap slot_map(const Call& c, const torch::Tensor& slots_dev,
+                        const torch::Tensor& slots_host, int B, int64_t S) {
+  SlotMap m;
+  m.host = host_lens(slots_host, B, c.who);
+  TORCH_CHECK(S <= INT_MAX, c.who, ": too many slots");
+  std::vector<bool> seen((size_t)std::max<int64_t>(S, 0), false);
+  for (int64_t s : m.host) {
+    TORCH_CHECK(s >= 0 && s < S, c.who, ": slot ", s, " is outside the pool of ", S);
+    TORCH_CHECK(!seen[(size_t)s], c.who, ": slot ", s, " is named twice");
+    seen[(size_t)s] = true;
+  }
+  m.dev = c.i32(slots_dev, "slots_dev", {B});
+  m.S = (int)S;
+  return m;
+}
+
 // sin/cos are the FULL tables (rows >= pos+Tn, C/2) fp32; fp32 LN weights are
 // used in place, others converted. pos_dev == nullptr: every sequence at
 // pos[0]; otherwise sequence b at pos[b] (host) == pos_dev[b] (device).
+// slots: sequence b in cache slot slots[b] of a pool (ragged calls only);
+// null: in cache row b.
 static torch::Tensor kv_append_impl(const Call& c, torch::Tensor qkv, torch::Tensor qw,
                                     torch::Tensor kw, torch::Tensor sin_t, torch::Tensor cos_t,
                                     torch::Tensor k_cache, torch::Tensor v_cache,
                                     const std::vector<int64_t>& pos, const int* pos_dev,
-                                    double eps) {
+                                    double eps, const torch::Tensor* slots_dev = nullptr,
+                                    const torch::Tensor* slots_host = nullptr) {
   const u16* qkvp = c.bf16(qkv, "qkv", {ANY, ANY, 3, ANY, ANY});
   int B = c.dim(qkv, 0), Tn = c.dim(qkv, 1), H = c.dim(qkv, 3), C = c.dim(qkv, 4);
   u16 *kcp, *vcp;
-  const int64_t Tmax = decode_caches(c, k_cache, v_cache, B, H, C, &kcp, &vcp);
+  int S = 0;
+  const int64_t Tmax =
+      decode_caches(c, k_cache, v_cache, B, H, C, &kcp, &vcp, slots_dev ? &S : nullptr);
+  SlotMap slots;
+  if (slots_dev) slots = slot_map(c, *slots_dev, *slots_host, B, S);
   TORCH_CHECK(Tn >= 1, "kv_append: no new tokens");
   TORCH_CHECK(qw.is_contiguous() && kw.is_contiguous(),
               "kv_append: LN weights must be contiguous");
@@ -741,8 +778,13 @@ static torch::Tensor kv_append_impl(const Call& c, torch::Tensor qkv, torch::Ten
   const int rpb = 4 * (WAVE / (C / 8));  // rows per 256-thread block
   const long grid = std::min((nrows + rpb - 1) / rpb, (long)16384);
   dispatch_flag(pos_dev != nullptr, [&](auto ragged) {
-    launch(kv_append_kernel<decltype(ragged)::value>, grid, 256, 0, qkvp, qwp, kwp, sinp, cosp,
-           fresh<u16>(q), kcp, vcp, B, Tn, H, C, (long)Tmax, (long)pos[0], pos_dev, (float)eps);
+    dispatch_flag(slots.dev != nullptr, [&](auto slotted) {
+      constexpr bool RAGGED = decltype(ragged)::value, SLOTS = decltype(slotted)::value;
+      if constexpr (RAGGED || !SLOTS)
+        launch(kv_append_kernel<RAGGED, SLOTS>, grid, 256, 0, qkvp, qwp, kwp, sinp, cosp,
+               fresh<u16>(q), kcp, vcp, B, Tn, H, C, (long)Tmax, (long)pos[0], pos_dev,
+               (float)eps, slots.dev, slots.S);
+    });
   });
   return q;
 }
@@ -766,6 +808,20 @@ torch::Tensor kv_append_ragged(torch::Tensor qkv, torch::Tensor qw, torch::Tenso
   auto pos = host_lens(pos_host, B, c.who);
   return kv_append_impl(c, qkv, qw, kw, sin_t, cos_t, k_cache, v_cache, pos,
                         c.i32(pos_dev, "pos_dev", {B}), eps);
+}
+
+torch::Tensor kv_append_slots(torch::Tensor qkv, torch::Tensor qw, torch::Tensor kw,
+                              torch::Tensor sin_t, torch::Tensor cos_t,
+                              torch::Tensor k_cache, torch::Tensor v_cache,
+                              torch::Tensor pos_dev, torch::Tensor pos_host,
+                              torch::Tensor slots_dev, torch::Tensor slots_host, double eps) {
+  Call c("kv_append_slots", qkv);
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(0) >= 1,
+              "kv_append: qkv must be (B,Tn,3,H,C) with B >= 1");
+  const int B = c.dim(qkv, 0);
+  auto pos = host_lens(pos_host, B, c.who);
+  return kv_append_impl(c, qkv, qw, kw, sin_t, cos_t, k_cache, v_cache, pos,
+                        c.i32(pos_dev, "pos_dev", {B}), eps, &slots_dev, &slots_host);
 }
 
 static int decode_cu_count() {
@@ -801,15 +857,21 @@ int64_t attn_decode_auto_splits(int64_t rows, int64_t kv_len, int64_t cus) {
 // [0, kv_len - Tq + i]. Returns o (B,Tq,H,C). lens_dev == nullptr: every
 // sequence has kv_lens[0] positions; otherwise sequence b has kv_lens[b]
 // (host) == lens_dev[b] (device), and num_splits = 0 applies the rule to the
-// longest.
+// longest. slots as in kv_append_impl.
 static torch::Tensor attn_decode_impl(const Call& c, torch::Tensor q, torch::Tensor k_cache,
                                       torch::Tensor v_cache,
                                       const std::vector<int64_t>& kv_lens,
-                                      const int* lens_dev, int64_t num_splits) {
+                                      const int* lens_dev, int64_t num_splits,
+                                      const torch::Tensor* slots_dev = nullptr,
+                                      const torch::Tensor* slots_host = nullptr) {
   const u16* qp = c.bf16(q, "q", {ANY, ANY, ANY, ANY});
   int B = c.dim(q, 0), H = c.dim(q, 1), Tq = c.dim(q, 2), C = c.dim(q, 3);
   u16 *kcp, *vcp;
-  const int64_t Tmax = decode_caches(c, k_cache, v_cache, B, H, C, &kcp, &vcp);
+  int pool = 0;
+  const int64_t Tmax =
+      decode_caches(c, k_cache, v_cache, B, H, C, &kcp, &vcp, slots_dev ? &pool : nullptr);
+  SlotMap slots;
+  if (slots_dev) slots = slot_map(c, *slots_dev, *slots_host, B, pool);
   int64_t kv_max = 0;
   for (int64_t kv_len : kv_lens) {
     TORCH_CHECK(kv_len <= Tmax, "attn_decode: kv_len ", kv_len, " exceeds the cache (", Tmax, ")");
@@ -838,9 +900,13 @@ static torch::Tensor attn_decode_impl(const Call& c, torch::Tensor q, torch::Ten
   const float scale = 1.0f / std::sqrt((float)C);
   dispatch_int<128, 64>(C, [&](auto cc) {
     dispatch_flag(lens_dev != nullptr, [&](auto ragged) {
-      launch(attn_decode_kernel<decltype(cc)::value, decltype(ragged)::value>, dim3(rows, S),
-             256, 0, qp, kcp, vcp, fresh<u16>(o), accp, mlp, H, Tq, (long)Tmax,
-             (int)kv_lens[0], lens_dev, S, scale);
+      dispatch_flag(slots.dev != nullptr, [&](auto slotted) {
+        constexpr bool RAGGED = decltype(ragged)::value, SLOTS = decltype(slotted)::value;
+        if constexpr (RAGGED || !SLOTS)
+          launch(attn_decode_kernel<decltype(cc)::value, RAGGED, SLOTS>, dim3(rows, S), 256, 0,
+                 qp, kcp, vcp, fresh<u16>(o), accp, mlp, H, Tq, (long)Tmax, (int)kv_lens[0],
+                 lens_dev, S, scale, slots.dev, slots.S);
+      });
     });
   });
   if (S > 1)
@@ -865,6 +931,19 @@ torch::Tensor attn_decode_ragged(torch::Tensor q, torch::Tensor k_cache,
                           c.i32(kv_lens_dev, "kv_lens_dev", {B}), num_splits);
 }
 
+torch::Tensor attn_decode_slots(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+                                torch::Tensor kv_lens_dev, torch::Tensor kv_lens_host,
+                                torch::Tensor slots_dev, torch::Tensor slots_host,
+                                int64_t num_splits) {
+  Call c("attn_decode_slots", q);
+  TORCH_CHECK(q.dim() == 4 && q.size(0) >= 1, "attn_decode: q must be (B,H,Tq,C) with B >= 1");
+  const int B = c.dim(q, 0);
+  auto lens = host_lens(kv_lens_host, B, c.who);
+  return attn_decode_impl(c, q, k_cache, v_cache, lens,
+                          c.i32(kv_lens_dev, "kv_lens_dev", {B}), num_splits, &slots_dev,
+                          &slots_host);
+}
+
 // ---------------------------------------------------------------------------
 // One token per row of logits (sampling.hip). top_k: 0 or >= V means all.
 torch::Tensor sample_tokens(torch::Tensor logits, double inv_t, int64_t top_k, int64_t seed,
@@ -887,6 +966,44 @@ torch::Tensor sample_tokens(torch::Tensor logits, double inv_t, int64_t top_k, i
            fresh<long>(out), V, it, has_k ? (int)top_k : 0, (uint32_t)s, (uint32_t)(s >> 32),
            (uint32_t)step);
   });
+  return out;
+}
+
+// Per-row parameters: row b draws as sample_tokens(X, inv_t[b], top_k[b],
+// seeds[b], steps[b]) draws row rows[b] of an X that holds logits[b] there.
+// inv_t[b] == 0 marks a greedy row (score = logit, top_k ignored, lowest index
+// of the maximum). The five host tensors, (B,) on the CPU, are the truth and
+// are validated. The kernel reads params_dev, (B, 6) int32 on the GPU, one
+// tensor so that a caller uploads it once for as long as the rows stay:
+//   [b] = {seed low word, seed high word, step, row, bits of fp32 inv_t, top_k}
+// (top_k clamped to INT_MAX; 0 or >= V: all). It is not compared with the host
+// values (that would be a sync): keeping them equal is the caller's contract.
+torch::Tensor sample_tokens_rows(torch::Tensor logits, torch::Tensor params_dev,
+                                 torch::Tensor inv_t, torch::Tensor top_k, torch::Tensor seeds,
+                                 torch::Tensor steps, torch::Tensor rows) {
+  Call c("sample_tokens_rows", logits);
+  const u16* lp = c.bf16(logits, "logits", {ANY, ANY});
+  const int B = c.dim(logits, 0), V = c.dim(logits, 1);
+  TORCH_CHECK(V >= 1, "sample_tokens_rows: empty rows");
+  TORCH_CHECK(!inv_t.is_cuda() && inv_t.dim() == 1 && inv_t.size(0) == B &&
+              inv_t.scalar_type() == torch::kFloat,
+              c.who, ": inv_t must be a CPU float32 tensor of ", B, " values");
+  auto itc = inv_t.contiguous();
+  for (int b = 0; b < B; ++b) {
+    const float it = itc.data_ptr<float>()[b];
+    TORCH_CHECK(std::isfinite(it) && it >= 0.f, c.who,
+                ": inv_t must be finite and > 0, or 0 for a greedy row, got ", it);
+  }
+  for (int64_t k : host_lens(top_k, B, c.who))
+    TORCH_CHECK(k >= 0, c.who, ": top_k >= 0 required (0: all), got ", k);
+  host_lens(seeds, B, c.who);  // any 64 bits
+  for (int64_t s : host_lens(steps, B, c.who))
+    TORCH_CHECK(s >= 0 && s <= (int64_t)UINT32_MAX, c.who, ": step must be in [0, 2^32), got ", s);
+  for (int64_t r : host_lens(rows, B, c.who))
+    TORCH_CHECK(r >= 0 && r <= (int64_t)UINT32_MAX, c.who, ": row must be in [0, 2^32), got ", r);
+  const int* pp = c.i32(params_dev, "params_dev", {B, SAMPLE_ROW_WORDS});
+  auto out = torch::empty({(long)B}, logits.options().dtype(torch::kLong));
+  launch(sample_tokens_rows_kernel, B, SAMPLE_THREADS, 0, lp, fresh<long>(out), V, pp);
   return out;
 }
 
@@ -943,10 +1060,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("attn_decode_ragged", &attn_decode_ragged, py::arg("q"), py::arg("k_cache"),
           py::arg("v_cache"), py::arg("kv_lens_dev"), py::arg("kv_lens_host"),
           py::arg("num_splits") = 0);
+  mod.def("kv_append_slots", &kv_append_slots, py::arg("qkv"), py::arg("qw"), py::arg("kw"),
+          py::arg("sin"), py::arg("cos"), py::arg("k_cache"), py::arg("v_cache"),
+          py::arg("pos_dev"), py::arg("pos_host"), py::arg("slots_dev"),
+          py::arg("slots_host"), py::arg("eps") = 1e-6);
+  mod.def("attn_decode_slots", &attn_decode_slots, py::arg("q"), py::arg("k_cache"),
+          py::arg("v_cache"), py::arg("kv_lens_dev"), py::arg("kv_lens_host"),
+          py::arg("slots_dev"), py::arg("slots_host"), py::arg("num_splits") = 0);
   mod.def("attn_decode_auto_splits", &attn_decode_auto_splits, py::arg("rows"),
           py::arg("kv_len"), py::arg("cus"));
   mod.def("sample_tokens", &sample_tokens, py::arg("logits"), py::arg("inv_t"),
           py::arg("top_k"), py::arg("seed"), py::arg("step"));
+  mod.def("sample_tokens_rows", &sample_tokens_rows, py::arg("logits"), py::arg("params_dev"),
+          py::arg("inv_t"), py::arg("top_k"), py::arg("seeds"), py::arg("steps"),
+          py::arg("rows"));
   mod.def("embedding_bwd", &embedding_bwd);
   mod.def("gelu_fwd", &gelu_fwd);
   mod.def("gelu_bwd", &gelu_bwd);

@@ -12,6 +12,12 @@
 // on its slice. The uniform instantiations compile to the same resource
 // figures as before the flag (profiles/decode.md).
 //
+// SLOTS (implies RAGGED) adds one level of indirection for a pool of S cache
+// slots: batch row b lives in slot slots[b], so its cache base is
+// (slots[b]*H + h)*Tmax*C instead of (b*H + h)*Tmax*C. One more 4-byte load
+// per row / block and nothing else: row b of a slotted call has the bits of
+// the ragged call on the gathered cache[slots].
+//
 // Decode attention is a memory-bound stream over K and V with one query row
 // per head: no MFMA, no LDS staging. K/V rows go straight to VGPRs with
 // 16-byte loads, C/8 lanes per key row.
@@ -22,7 +28,10 @@
 // + h) and the same row body (qk_ln_rope_row, norms.hip); only the position
 // (pos + t) and the destinations differ. RAGGED: sequence b starts at
 // pos_b[b] instead of pos (one more 4-byte load per row, nothing else).
-template <bool RAGGED>
+// SLOTS: the cache rows are those of slot slots[b] of S. The binding validated
+// the host copy of the map; a device copy that names a slot outside [0, S)
+// writes nothing for that row (neither cache nor q).
+template <bool RAGGED, bool SLOTS = false>
 __global__ void kv_append_kernel(const u16* __restrict__ qkv,
                                  const float* __restrict__ qw,
                                  const float* __restrict__ kw,
@@ -31,7 +40,9 @@ __global__ void kv_append_kernel(const u16* __restrict__ qkv,
                                  u16* __restrict__ q, u16* __restrict__ k_cache,
                                  u16* __restrict__ v_cache,
                                  int B, int Tn, int H, int C, long Tmax, long pos,
-                                 const int* __restrict__ pos_b, float eps) {
+                                 const int* __restrict__ pos_b, float eps,
+                                 const int* __restrict__ slots, int S) {
+  static_assert(RAGGED || !SLOTS, "SLOTS implies RAGGED");
   const int LPR = C / 8;                 // lanes per row (8 or 16)
   const int RPW = WAVE / LPR;            // rows per wave
   const int sub = lane_id() % LPR;
@@ -52,8 +63,13 @@ __global__ void kv_append_kernel(const u16* __restrict__ qkv,
       // must not write outside the cache
       if (pos < 0 || pos + Tn > Tmax) continue;
     }
+    long cb = b;                         // cache row of the batch
+    if constexpr (SLOTS) {
+      cb = slots[b];
+      if (cb < 0 || cb >= S) continue;
+    }
     const u16x8 raw = *(const u16x8*)(qkv + ((bt * 3 + role) * H + h) * C + sub * 8);
-    const long cache_off = ((b * H + h) * Tmax + pos + t) * C + sub * 8;
+    const long cache_off = ((cb * H + h) * Tmax + pos + t) * C + sub * 8;
     if (role == 2) {
       *(u16x8*)(v_cache + cache_off) = raw;
       continue;
@@ -85,7 +101,12 @@ DEVINL float decode_weight(float m, float m_ref) {
 // empty. No cache row >= limit is ever loaded (the cache tail is
 // uninitialised memory). RAGGED: kv_len is read per sequence from
 // kv_lens[b]; a short sequence next to a long one has short, possibly empty,
-// slices, and everything else is the same code.
+// slices, and everything else is the same code. SLOTS: the keys of sequence b
+// are those of cache slot slots[b] of S. The host copy of the map is the
+// truth; for a device copy that names a slot outside [0, S) the block treats
+// its row as kv_len = Tq in slot 0: it reads rows [0, Tq) of a cache that
+// exists, never anything outside it, and slice 0 still writes its output or
+// partials (whatever those rows hold).
 //
 // 256 threads form G = 256/(C/8) lane groups; group g takes keys k0+g,
 // k0+g+G, ... in batches of U keys whose K and V loads (2*U 16-byte loads per
@@ -94,13 +115,14 @@ DEVINL float decode_weight(float m, float m_ref) {
 // and its own 8 columns of acc. Groups merge by shuffles, waves through LDS.
 // num_splits == 1: writes o (B,Tq,H,C) bf16. Otherwise writes the slice's
 // fp32 (m, l) to ws_ml[row][split][2] and acc to ws_acc[row][split][C].
-template <int C, bool RAGGED>
+template <int C, bool RAGGED, bool SLOTS = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k_cache,
     const u16* __restrict__ v_cache, u16* __restrict__ o,
     float* __restrict__ ws_acc, float* __restrict__ ws_ml,
     int H, int Tq, long Tmax, int kv_len, const int* __restrict__ kv_lens,
-    int num_splits, float scale) {
+    int num_splits, float scale, const int* __restrict__ slots, int S) {
+  static_assert(RAGGED || !SLOTS, "SLOTS implies RAGGED");
   constexpr int LPR = C / 8;
   constexpr int G = 256 / LPR;
   constexpr int U = 4;
@@ -109,17 +131,27 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   const int split = blockIdx.y;
   const int i = row % Tq;
   const int bh = row / Tq;
+  int cbh = bh;                          // (cache row of the batch)*H + h
   // min: a device copy that disagrees with the validated host one must not
   // read past the cache
-  if constexpr (RAGGED) kv_len = min(kv_lens[bh / H], (int)Tmax);
+  if constexpr (SLOTS) {
+    const int slot = slots[bh / H];
+    const bool ok = (unsigned)slot < (unsigned)S;
+    // the length load inside the guard: written after it, the same code
+    // takes 15 more VGPRs (profiles/decode.md)
+    kv_len = ok ? min(kv_lens[bh / H], (int)Tmax) : Tq;
+    cbh = (ok ? slot : 0) * H + bh % H;
+  } else if constexpr (RAGGED) {
+    kv_len = min(kv_lens[bh / H], (int)Tmax);
+  }
   const int limit = kv_len - Tq + i + 1;
   const int per = (limit + num_splits - 1) / num_splits;
   const int k0 = split * per;
   const int k1 = min(limit, k0 + per);
   const int sub = threadIdx.x % LPR;
   const int g = threadIdx.x / LPR;
-  const u16* kb = k_cache + (long)bh * Tmax * C + sub * 8;
-  const u16* vb = v_cache + (long)bh * Tmax * C + sub * 8;
+  const u16* kb = k_cache + (long)cbh * Tmax * C + sub * 8;
+  const u16* vb = v_cache + (long)cbh * Tmax * C + sub * 8;
 
   float qf[8];
   {

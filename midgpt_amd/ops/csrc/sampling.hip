@@ -83,51 +83,51 @@ DEVINL bool sample_better(float s2, int v2, float s, int v) {
   return s2 > s || (s2 == s && v2 < v);
 }
 
-// top_k: 1 <= top_k < V where HAS_K (the binding sees to it).
-template <bool HAS_K>
-__global__ __launch_bounds__(SAMPLE_THREADS) void sample_tokens_kernel(
-    const u16* __restrict__ logits, long* __restrict__ out, int V, float inv_t, int top_k,
-    uint32_t seed_lo, uint32_t seed_hi, uint32_t step) {
-  const int tid = threadIdx.x, lane = lane_id(), wid = wave_id();
-  const uint32_t b = blockIdx.x;
-  const u16* __restrict__ row = logits + (long)b * V;
-  const bool vec = ((uintptr_t)row & 15) == 0;
+// The key of the row's k-th largest logit, 1 <= top_k < V: two histogram
+// passes, block-uniform. hist (one bin per thread), wtot and sel are the
+// kernel's LDS (a kernel that never selects gets none).
+DEVINL unsigned sample_kth_key(const u16* __restrict__ row, int V, bool vec, int top_k,
+                               int* hist, int* wtot, int* sel) {
+  const int tid = threadIdx.x;
   constexpr int STRIDE = SAMPLE_THREADS * 8;
-
-  __shared__ int hist[SAMPLE_THREADS];  // one bin per thread
-  __shared__ int wtot[SAMPLE_THREADS / WAVE];
-  __shared__ int sel[2];
-  __shared__ float red_s[SAMPLE_THREADS / WAVE];
-  __shared__ int red_v[SAMPLE_THREADS / WAVE];
-
-  unsigned kth = 0;  // candidates: key >= kth
-  if (HAS_K) {
-    int k = top_k;
-    unsigned hi = 0;
+  unsigned kth = 0;
+  int k = top_k;
+  unsigned hi = 0;
 #pragma unroll 1
-    for (int pass = 0; pass < 2; ++pass) {
-      if (tid < 2) sel[tid] = tid;  // overwritten below: the counts total at least k
-      hist[tid] = 0;
-      __syncthreads();
-      for (int i = tid * 8; i < V; i += STRIDE) {
-        u16 h[8];
-        const int n = sample_load8(row, i, V, vec, h);
+  for (int pass = 0; pass < 2; ++pass) {
+    if (tid < 2) sel[tid] = tid;  // overwritten below: the counts total at least k
+    hist[tid] = 0;
+    __syncthreads();
+    for (int i = tid * 8; i < V; i += STRIDE) {
+      u16 h[8];
+      const int n = sample_load8(row, i, V, vec, h);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const unsigned key = sample_key(h[j]);
-          if (j < n && (pass == 0 || (key >> 8) == hi))
-            atomicAdd(&hist[pass == 0 ? key >> 8 : key & 0xffu], 1);
-        }
+      for (int j = 0; j < 8; ++j) {
+        const unsigned key = sample_key(h[j]);
+        if (j < n && (pass == 0 || (key >> 8) == hi))
+          atomicAdd(&hist[pass == 0 ? key >> 8 : key & 0xffu], 1);
       }
-      __syncthreads();
-      sample_select_bin(hist, k, wtot, sel);
-      if (pass == 0) hi = (unsigned)sel[0];
-      else kth = (hi << 8) | (unsigned)sel[0];
-      k = sel[1];
-      __syncthreads();
     }
+    __syncthreads();
+    sample_select_bin(hist, k, wtot, sel);
+    if (pass == 0) hi = (unsigned)sel[0];
+    else kth = (hi << 8) | (unsigned)sel[0];
+    k = sel[1];
+    __syncthreads();
   }
+  return kth;
+}
 
+// Scores the candidates (key >= kth where HAS_K, else all) of the row with
+// the noise of Philox row word `b`, reduces over the workgroup and returns the
+// token in thread 0. GREEDY_OPT: with greedy set (block-uniform) the score is
+// the logit alone and no noise is drawn.
+template <bool HAS_K, bool GREEDY_OPT>
+DEVINL int sample_pick(const u16* __restrict__ row, int V, bool vec, unsigned kth, float inv_t,
+                       uint32_t seed_lo, uint32_t seed_hi, uint32_t b, uint32_t step,
+                       bool greedy, float* red_s, int* red_v) {
+  const int tid = threadIdx.x, lane = lane_id(), wid = wave_id();
+  constexpr int STRIDE = SAMPLE_THREADS * 8;
   float best_s = -INFINITY;
   int best_v = INT_MAX;
   for (int i = tid * 8; i < V; i += STRIDE) {
@@ -143,6 +143,16 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_tokens_kernel(
         any |= cand[j];
       }
       if (!any) continue;
+      if (GREEDY_OPT && greedy) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (!cand[j]) continue;
+          const float s = b2f(h[half * 4 + j]);
+          const int v = i + half * 4 + j;
+          if (sample_better(s, v, best_s, best_v)) { best_s = s; best_v = v; }
+        }
+        continue;
+      }
       const PhiloxWords r =
           sample_words(seed_lo, seed_hi, b, step, (uint32_t)(i >> 2) + half);
 #pragma unroll
@@ -167,8 +177,66 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_tokens_kernel(
   __syncthreads();
   if (tid == 0) {
     for (int w = 1; w < SAMPLE_THREADS / WAVE; ++w)
-      if (sample_better(red_s[w], red_v[w], best_s, best_v)) { best_s = red_s[w]; best_v = red_v[w]; }
-    // a row of NaN (outside the contract) leaves no winner: still an index
-    out[b] = best_v < V ? best_v : 0;
+      if (sample_better(red_s[w], red_v[w], best_s, best_v)) {
+        best_s = red_s[w];
+        best_v = red_v[w];
+      }
   }
+  // a row of NaN (outside the contract) leaves no winner: still an index
+  return best_v < V ? best_v : 0;
+}
+
+// top_k: 1 <= top_k < V where HAS_K (the binding sees to it).
+template <bool HAS_K>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_tokens_kernel(
+    const u16* __restrict__ logits, long* __restrict__ out, int V, float inv_t, int top_k,
+    uint32_t seed_lo, uint32_t seed_hi, uint32_t step) {
+  const uint32_t b = blockIdx.x;
+  const u16* __restrict__ row = logits + (long)b * V;
+  const bool vec = ((uintptr_t)row & 15) == 0;
+  __shared__ int hist[SAMPLE_THREADS];
+  __shared__ int wtot[SAMPLE_THREADS / WAVE];
+  __shared__ int sel[2];
+  __shared__ float red_s[SAMPLE_THREADS / WAVE];
+  __shared__ int red_v[SAMPLE_THREADS / WAVE];
+  unsigned kth = 0;  // candidates: key >= kth
+  if (HAS_K) kth = sample_kth_key(row, V, vec, top_k, hist, wtot, sel);
+  const int tok = sample_pick<HAS_K, false>(row, V, vec, kth, inv_t, seed_lo, seed_hi, b, step,
+                                            false, red_s, red_v);
+  if (threadIdx.x == 0) out[b] = tok;
+}
+
+// Per-row parameters: row b of the launch draws by the definition above with
+// its own values, params[b] = SAMPLE_ROW_WORDS int32 words
+//   {seed_lo, seed_hi, step, row, bits of fp32 inv_t, top_k}
+// where `row` is the Philox counter word that sample_tokens_kernel fills with
+// the batch index, so out[b] is what sample_tokens_kernel gives row `row` of a
+// batch whose row `row` holds these logits. top_k outside [1, V): all entries
+// (the choice is block-uniform: one workgroup per row). inv_t <= 0 marks a
+// greedy row: score = logit, top_k ignored, lowest index of the maximum.
+constexpr int SAMPLE_ROW_WORDS = 6;
+
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_tokens_rows_kernel(
+    const u16* __restrict__ logits, long* __restrict__ out, int V,
+    const int* __restrict__ params) {
+  const uint32_t b = blockIdx.x;
+  const u16* __restrict__ row = logits + (long)b * V;
+  const bool vec = ((uintptr_t)row & 15) == 0;
+  const int* __restrict__ p = params + (long)b * SAMPLE_ROW_WORDS;
+  const uint32_t seed_lo = (uint32_t)p[0], seed_hi = (uint32_t)p[1];
+  const uint32_t step = (uint32_t)p[2], rowctr = (uint32_t)p[3];
+  const float inv_t = __int_as_float(p[4]);
+  const int top_k = p[5];
+  const bool greedy = !(inv_t > 0.f);
+  __shared__ int hist[SAMPLE_THREADS];
+  __shared__ int wtot[SAMPLE_THREADS / WAVE];
+  __shared__ int sel[2];
+  __shared__ float red_s[SAMPLE_THREADS / WAVE];
+  __shared__ int red_v[SAMPLE_THREADS / WAVE];
+  unsigned kth = 0;  // key >= 0: every entry is a candidate
+  if (!greedy && top_k >= 1 && top_k < V)
+    kth = sample_kth_key(row, V, vec, top_k, hist, wtot, sel);
+  const int tok = sample_pick<true, true>(row, V, vec, kth, inv_t, seed_lo, seed_hi, rowctr,
+                                          step, greedy, red_s, red_v);
+  if (threadIdx.x == 0) out[b] = tok;
 }

@@ -1,6 +1,6 @@
 """The extension's interface in fp32 torch: one plain function (no autograd)
-per entry point in ``ops.BACKEND_API``, ``ops.RAGGED_API`` and
-``ops.SAMPLING_API``, taking the same positional arguments
+per entry point in ``ops.BACKEND_API``, ``ops.RAGGED_API``,
+``ops.SAMPLING_API`` and ``ops.SLOT_API``, taking the same positional arguments
 as the ``_C`` binding of that name and returning as many results with the
 same shapes and dtypes. ``ops._backend`` hands out this module wherever the
 HIP extension does not run: on the CPU and under ``MIDGPT_FORCE_REF=1``.
@@ -225,6 +225,47 @@ def attn_decode_ragged(q, k_cache, v_cache, kv_lens_dev, kv_lens_host, num_split
                       for b in range(B)], dim=0)
 
 
+# Slotted decode (ops.SLOT_API): batch row b lives in cache slot slots[b] of a
+# pool (S,H,Tmax,C), S >= B. The ragged op on the one-slot view of each row,
+# so row b has the bits of the ragged call on the gathered cache[slots].
+def _host_slots(t, B, S, who):
+    slots = _host_lens(t, B, who)
+    if S < B:
+        raise RuntimeError(f"{who}: a pool of {S} slots cannot hold {B} rows")
+    for s in slots:
+        if not 0 <= s < S:
+            raise RuntimeError(f"{who}: slot {s} is outside the pool of {S}")
+    if len(set(slots)) != B:
+        raise RuntimeError(f"{who}: a slot is named twice in {slots}")
+    return slots
+
+
+def kv_append_slots(qkv, qw, kw, sin, cos, k_cache, v_cache, pos_dev, pos_host,
+                    slots_dev, slots_host, eps):
+    B = qkv.shape[0]
+    pos = _host_lens(pos_host, B, "kv_append_slots")
+    slots = _host_slots(slots_host, B, k_cache.shape[0], "kv_append_slots")
+    Tn, Tmax = qkv.shape[1], k_cache.shape[2]
+    for p in pos:  # every position before the first write, as the binding does
+        if p < 0 or p + Tn > Tmax:
+            raise RuntimeError(f"kv_append: rows [{p}, {p + Tn}) do not fit a "
+                               f"cache of {Tmax} rows")
+    return torch.cat([kv_append_ragged(qkv[b:b + 1], qw, kw, sin, cos,
+                                       k_cache[s:s + 1], v_cache[s:s + 1], None,
+                                       torch.tensor([pos[b]]), eps)
+                      for b, s in enumerate(slots)], dim=0)
+
+
+def attn_decode_slots(q, k_cache, v_cache, kv_lens_dev, kv_lens_host, slots_dev,
+                      slots_host, num_splits):
+    B = q.shape[0]
+    lens = _host_lens(kv_lens_host, B, "attn_decode_slots")
+    slots = _host_slots(slots_host, B, k_cache.shape[0], "attn_decode_slots")
+    return torch.cat([attn_decode_ragged(q[b:b + 1], k_cache[s:s + 1], v_cache[s:s + 1],
+                                         None, torch.tensor([lens[b]]), num_splits)
+                      for b, s in enumerate(slots)], dim=0)
+
+
 # Seeded token sampling (ops.SAMPLING_API): top-k + Gumbel-max, the
 # definition of csrc/sampling.hip in fp32 on the logits' device. The Philox
 # words come from the host mirror, so one (seed, step) gives one stream on
@@ -239,12 +280,21 @@ def sample_tokens(logits, inv_t, top_k, seed, step):
     if top_k < 0:
         raise RuntimeError(f"sample_tokens: top_k >= 0 required (0: all), got {top_k}")
     B, V = logits.shape
-    words = ref.sample_words(B, V, seed, step)
-    m = torch.from_numpy((words >> 9).astype("int32"))
-    t = (2 * m + 1).to(torch.float32) * 2.0 ** -24   # exact: < 2^24
-    noise = -torch.log(-torch.log(t))
+    return _sample_from_words(logits, inv_t, top_k, ref.sample_words(B, V, seed, step))
+
+
+def _sample_from_words(logits, inv_t, top_k, words):
+    """The draw of every row of logits (B, V) from its Philox words, uint32
+    (B, V); words None: greedy, the score is the logit alone."""
+    B, V = logits.shape
     lf = logits.float()
-    score = lf * inv_t + noise.to(logits.device)
+    if words is None:
+        score = lf.clone()
+    else:
+        m = torch.from_numpy((words >> 9).astype("int32"))
+        t = (2 * m + 1).to(torch.float32) * 2.0 ** -24   # exact: < 2^24
+        noise = -torch.log(-torch.log(t))
+        score = lf * inv_t + noise.to(logits.device)
     if 1 <= top_k < V:
         kth = torch.topk(lf, top_k, dim=-1).values[:, -1:]
         score = score.masked_fill(lf < kth, float("-inf"))
@@ -254,6 +304,40 @@ def sample_tokens(logits, inv_t, top_k, seed, step):
     idx = torch.arange(V, device=logits.device).expand(B, V)
     tok = torch.where(score == best, idx, V).min(dim=-1).values
     return tok.clamp_(max=V - 1)   # a NaN row (outside the contract) has no maximum
+
+
+def sample_tokens_rows(logits, params_dev, inv_t, top_k, seeds, steps, rows):
+    """Row b by the definition of ``sample_tokens`` with its own (inv_t[b],
+    top_k[b], seeds[b], steps[b]) and Philox row word rows[b]; inv_t[b] == 0:
+    greedy (the logit alone, top_k ignored, lowest index of the maximum). The
+    five host tensors are validated as the binding does; params_dev is what
+    the kernel reads and is unused here."""
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise RuntimeError(f"sample_tokens_rows: logits must be (B, V), got {tuple(logits.shape)}")
+    B, V = logits.shape
+    who = "sample_tokens_rows"
+    if inv_t.is_cuda or inv_t.shape != (B,) or inv_t.dtype != torch.float32:
+        raise RuntimeError(f"{who}: inv_t must be a CPU float32 tensor of {B} values")
+    inv_t = [float(x) for x in inv_t.tolist()]
+    top_k, seeds = _host_lens(top_k, B, who), _host_lens(seeds, B, who)
+    steps, rows = _host_lens(steps, B, who), _host_lens(rows, B, who)
+    for b in range(B):
+        if not (math.isfinite(inv_t[b]) and inv_t[b] >= 0):
+            raise RuntimeError(f"{who}: inv_t must be finite and > 0, or 0 for a "
+                               f"greedy row, got {inv_t[b]}")
+        if top_k[b] < 0:
+            raise RuntimeError(f"{who}: top_k >= 0 required (0: all), got {top_k[b]}")
+        if not (0 <= steps[b] < 1 << 32 and 0 <= rows[b] < 1 << 32):
+            raise RuntimeError(f"{who}: step and row must be in [0, 2^32), got "
+                               f"{steps[b]}, {rows[b]}")
+    out = []
+    for b in range(B):
+        if inv_t[b] == 0:
+            out.append(_sample_from_words(logits[b:b + 1], 1.0, 0, None))
+        else:
+            words = ref.sample_words(1, V, seeds[b], steps[b], row0=rows[b])
+            out.append(_sample_from_words(logits[b:b + 1], inv_t[b], top_k[b], words))
+    return torch.cat(out) if out else torch.empty(0, dtype=torch.int64, device=logits.device)
 
 
 # GELU (tanh approximation)

@@ -120,11 +120,11 @@ def attn_dropout_keep(seed: int, B: int, H: int, T: int, p: float) -> torch.Tens
 SAMPLE_DOMAIN = 0x53414D50  # "SAMP": counter word c3 of the sampling stream
 
 
-def sample_words(B: int, V: int, seed: int, step: int) -> np.ndarray:
+def sample_words(B: int, V: int, seed: int, step: int, row0: int = 0) -> np.ndarray:
     """Bit-exact host mirror of csrc/philox.h:sample_words: uint32 (B, V),
     the word of vocabulary entry v of logits row b at token ``step``.
-    Key = 64-bit seed, counter = (v >> 2, b, step, SAMPLE_DOMAIN), entry v
-    takes word v & 3."""
+    Key = 64-bit seed, counter = (v >> 2, row0 + b, step, SAMPLE_DOMAIN),
+    entry v takes word v & 3."""
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     step = int(step)
     if not 0 <= step < 1 << 32:
@@ -133,7 +133,7 @@ def sample_words(B: int, V: int, seed: int, step: int) -> np.ndarray:
     n4 = (V + 3) // 4
     shape = (B, n4)
     c0 = np.broadcast_to(np.arange(n4, dtype=np.uint64)[None, :], shape)
-    c1 = np.broadcast_to(np.arange(B, dtype=np.uint64)[:, None], shape)
+    c1 = np.broadcast_to(np.arange(row0, row0 + B, dtype=np.uint64)[:, None], shape)
     c2 = np.full(shape, step, dtype=np.uint64)
     c3 = np.full(shape, SAMPLE_DOMAIN, dtype=np.uint64)
     words = np.stack(_philox4x32_10(c0, c1, c2, c3, k0, k1), axis=2)  # (B,n4,4)

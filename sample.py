@@ -4,7 +4,9 @@
 
 ``--start`` may be given several times, or ``--start_file`` names a file with
 one prompt per line: more than one prompt decodes as one ragged batch
-(``generate_ragged``), one sample per prompt, ``--num_samples`` ignored.
+(``generate_ragged``), one sample per prompt, ``--num_samples`` ignored; with
+``--slots N`` they go through ``generate_continuous`` on N cache slots instead
+(continuous batching: there may be more prompts than slots).
 
 Loads config.json + the latest checkpoint from the rundir, rebuilds the
 model, and generates. Improvement over the reference (which re-runs a full
@@ -20,7 +22,7 @@ import torch
 
 from midgpt_amd import ops
 from midgpt_amd.config import ExperimentConfig
-from midgpt_amd.generate import generate, generate_ragged
+from midgpt_amd.generate import generate, generate_continuous, generate_ragged
 from midgpt_amd.models.gpt import GPT
 from midgpt_amd.utils import checkpoint as ckpt
 
@@ -93,6 +95,9 @@ def main():
     p.add_argument("--max_new_tokens", type=int, default=200)
     p.add_argument("--temperature", type=float, default=0.8)
     p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--slots", type=int, default=0,
+                   help="several prompts: decode them by continuous batching on "
+                        "this many cache slots (0: one ragged batch)")
     args = p.parse_args()
 
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -109,9 +114,14 @@ def main():
     if len(starts) > 1:
         prompts = [torch.tensor(encode(s), dtype=torch.int64, device=device)
                    for s in starts]
-        outs = generate_ragged(model, prompts, args.max_new_tokens,
-                               temperature=args.temperature, top_k=args.top_k,
-                               eos_id=args.eos_id, seed=seed)
+        if args.slots > 0:
+            outs = generate_continuous(model, prompts, args.max_new_tokens,
+                                       temperature=args.temperature, top_k=args.top_k,
+                                       eos_id=args.eos_id, num_slots=args.slots, seed=seed)
+        else:
+            outs = generate_ragged(model, prompts, args.max_new_tokens,
+                                   temperature=args.temperature, top_k=args.top_k,
+                                   eos_id=args.eos_id, seed=seed)
         for o in outs:
             print(decode(o.tolist()))
             print("---------------")

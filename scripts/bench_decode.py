@@ -38,6 +38,19 @@
                     to end: the --which ragged set-up at temperature 0.8,
                     top_k 50 with seed=, the same with a CPU generator, and
                     greedy, alternating.
+  --which slots     attn_decode_slots and kv_append_slots with the identity map
+                    and with a permuted map against the ragged ops on the same
+                    ring of caches (a cache of the ring is the pool, S = B),
+                    the three alternating x 3, at the B8 / B64 shapes of the
+                    ragged table.
+  --which continuous  openwebtext_xl architecture, random weights, greedy: 32
+                    requests, prompt lengths cycling through the eight of the
+                    ragged case, budgets cycling through 16, 64, 128, 256 new
+                    tokens. DecodeScheduler with 8 slots against
+                    generate_ragged on the requests in arrival order, four
+                    batches of 8 (each batch runs to its longest budget), the
+                    two alternating in this process, each warmed up. Tokens/s =
+                    tokens requested / wall time.
 """
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -221,6 +234,110 @@ def bench_ragged_e2e(reps, n_new=128):
           flush=True)
 
 
+def bench_slots(B, H, C, kv_len):
+    """attn_decode_slots (identity map, permuted map) against
+    attn_decode_ragged, the three alternating over the same ring; then the
+    same for kv_append at Tn = 1."""
+    nbytes = 2 * B * H * kv_len * C * 2
+    ring = max(1, min(32, -(-RING_BYTES // nbytes)))
+    caches = [(torch.randn(B, H, kv_len, C, device=DEV, dtype=BF),
+               torch.randn(B, H, kv_len, C, device=DEV, dtype=BF))
+              for _ in range(ring)]
+    q = torch.randn(B, H, 1, C, device=DEV, dtype=BF)
+    lens_host = torch.full((B,), kv_len, dtype=torch.int64)
+    lens_dev = lens_host.to(device=DEV, dtype=torch.int32)
+    ident = torch.arange(B)
+    perm = torch.randperm(B, generator=torch.Generator().manual_seed(0))
+    maps = {"slots identity": (ident.to(device=DEV, dtype=torch.int32), ident),
+            "slots permuted": (perm.to(device=DEV, dtype=torch.int32), perm)}
+    iters = 200 if nbytes < (64 << 20) else 50
+    paths = {"ragged": [(lambda k=k, v=v: ops._C.attn_decode_ragged(
+        q, k, v, lens_dev, lens_host, 0)) for k, v in caches]}
+    for name, (sd, sh) in maps.items():
+        paths[name] = [(lambda k=k, v=v, sd=sd, sh=sh: ops._C.attn_decode_slots(
+            q, k, v, lens_dev, lens_host, sd, sh, 0)) for k, v in caches]
+    res = {name: [] for name in paths}
+    for _ in range(3):                                    # alternating
+        for name, fns in paths.items():
+            res[name].append(time_ring(fns, iters) * 1e6)
+    for name, r in res.items():
+        print(f"attn_decode {name:14s} B{B} H{H} C{C} kv{kv_len} auto: "
+              f"{statistics.median(r):9.1f} us (min {min(r):.1f} max {max(r):.1f})",
+              flush=True)
+    qkv = torch.randn(B, 1, 3, H, C, device=DEV, dtype=BF)
+    qw = torch.ones(C, device=DEV)
+    sin, cos = (t.contiguous() for t in ref.rope_tables(C, kv_len, device=DEV))
+    pos_host = torch.full((B,), kv_len - 1, dtype=torch.int64)
+    pos_dev = pos_host.to(device=DEV, dtype=torch.int32)
+    kc, vc = caches[0]
+    paths = {"ragged": [lambda: ops._C.kv_append_ragged(qkv, qw, qw, sin, cos, kc, vc, pos_dev,
+                                                        pos_host, 1e-6)]}
+    for name, (sd, sh) in maps.items():
+        paths[name] = [lambda sd=sd, sh=sh: ops._C.kv_append_slots(
+            qkv, qw, qw, sin, cos, kc, vc, pos_dev, pos_host, sd, sh, 1e-6)]
+    res = {name: [] for name in paths}
+    for _ in range(3):
+        for name, fns in paths.items():
+            res[name].append(time_ring(fns, 500) * 1e6)
+    for name, r in res.items():
+        print(f"kv_append   {name:14s} B{B} H{H} C{C} Tn1: "
+              f"{statistics.median(r):9.1f} us (min {min(r):.1f} max {max(r):.1f})",
+              flush=True)
+    del caches
+
+
+def bench_continuous(reps, n_req=32, num_slots=8):
+    from midgpt_amd.generate import DecodeScheduler, generate_ragged
+    model, cfg = xl_model()
+    lens = [16, 48, 96, 160, 240, 320, 416, 512]
+    budgets = [16, 64, 128, 256]
+    g = torch.Generator().manual_seed(0)
+    reqs = [(torch.randint(0, cfg.vocab_size, (lens[i % 8],), generator=g).to(DEV),
+             budgets[i % 4]) for i in range(n_req)]
+    asked = sum(n for _, n in reqs)
+    print(f"continuous: openwebtext_xl, {n_req} requests, prompts cycling {lens}, budgets "
+          f"cycling {budgets} ({asked} tokens requested), greedy, {num_slots} slots; time "
+          "includes the prompts", flush=True)
+
+    def continuous(rs):
+        sched = DecodeScheduler(model, num_slots)
+        hs = [sched.submit(p, n, temperature=0.0) for p, n in rs]
+        sched.run()
+        assert [h.tokens.numel() for h in hs] == [p.numel() + n for p, n in rs]
+
+    def ragged_batches(rs):
+        for i in range(0, len(rs), num_slots):
+            batch = rs[i:i + num_slots]
+            outs = generate_ragged(model, [p for p, _ in batch], max(n for _, n in batch),
+                                   temperature=0.0)
+            outs = [o[:p.numel() + n] for o, (p, n) in zip(outs, batch)]
+            assert [o.numel() for o in outs] == [p.numel() + n for p, n in batch]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn(reqs)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    paths = {"DecodeScheduler 8 slots": continuous, "generate_ragged 4 x B=8": ragged_batches}
+    warm = [(p, 8) for p, _ in reqs[:2 * num_slots]]
+    for fn in paths.values():                             # warm up both
+        fn(warm)
+    res = {name: [] for name in paths}
+    for _ in range(reps):                                 # alternating
+        for name, fn in paths.items():
+            res[name].append(timed(fn))
+    for name, ts in res.items():
+        tps = sorted(asked / t for t in ts)
+        print(f"continuous {name:24s}: tokens/s median {statistics.median(tps):8.1f} "
+              f"min {tps[0]:8.1f} max {tps[-1]:8.1f}  (wall median "
+              f"{statistics.median(ts)*1e3:8.1f} ms) over {reps} runs", flush=True)
+    a, b = (statistics.median(res[k]) for k in res)
+    print(f"continuous speed ratio of medians (scheduler over ragged batches): {b/a:.2f}x",
+          flush=True)
+
+
 def bench_sample_kernel(B, V, top_k):
     from midgpt_amd.generate import _sample
     ring = [(4.0 * torch.randn(B, V, device=DEV)).to(BF) for _ in range(4)]
@@ -354,7 +471,8 @@ def run_count(n_new, sampled):
 
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
-    p.add_argument("--which", default="all", choices=["all", "kernels", "ragged", "e2e", "count", "sampling"])
+    p.add_argument("--which", default="all", choices=["all", "kernels", "ragged", "e2e", "count", "sampling", "slots",
+                            "continuous"])
     p.add_argument("--sweep", action="store_true")
     p.add_argument("--reps", type=int, default=3)
     p.add_argument("--new", type=int, default=32)
@@ -384,5 +502,12 @@ if __name__ == "__main__":
             for top_k in (None, 50):
                 bench_sample_kernel(B, 50304, top_k)
         bench_sample_e2e(max(3, args.reps))
+    if args.which in ("all", "slots"):
+        for B in (8, 64):
+            for kv in (128, 1024):
+                bench_slots(B, 16, 128, kv)
+            bench_slots(B, 32, 128, 4096)
+    if args.which in ("all", "continuous"):
+        bench_continuous(max(3, args.reps))
     if args.which == "count":
         run_count(args.new, args.sampled)

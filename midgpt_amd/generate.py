@@ -27,7 +27,10 @@ finished) and does not compact the batch when sequences finish.
 slots, a step runs the rows named by a slot map (``decode_step_slots`` on
 ``ops.kv_append_slots`` / ``ops.decode_attention_slots``), requests join and
 leave between steps, and every request samples with its own parameters
-(``ops.sample_tokens_rows``), so its text does not depend on its batch.
+(``ops.sample_tokens_rows``), so its text does not depend on its batch. With
+``num_pages`` the pool is a ``PagedKVCache``: a request holds only the pages
+it can write, found through a block table (``decode_step_paged`` on
+``ops.kv_append_paged`` / ``ops.decode_attention_paged``).
 """
 from __future__ import annotations
 
@@ -500,6 +503,195 @@ def decode_step_slots(model, idx_new: torch.Tensor, cache: KVCache, slots,
                           None if pending is None else pending[:, -1:])
 
 
+class PagedKVCache:
+    """K/V of every layer in ``num_pages`` pages of ``page_size`` positions,
+    shared by ``num_seats`` sequences: one buffer (n_layer, 2, num_pages, H,
+    page_size, C) with per-layer pool views ``k[l]`` / ``v[l]`` of shape
+    (num_pages, H, page_size, C). Position p of the sequence in seat s lives at
+    row p % page_size of page ``table[s][p // page_size]``.
+
+    Kept on the host, per seat: the page list ``pages[s]``, the length
+    ``lens[s]`` and the capacity ``cap[s]`` = pages * page_size (at most
+    block_size), with the (num_seats, MP) block table ``table`` (int32, -1
+    where no page is assigned; MP = block_size / page_size). ``alloc`` hands
+    out the lowest free page numbers first, so a run is deterministic;
+    ``free`` returns a seat's pages. Both change the host side only:
+    ``upload`` (or a caller that folds ``host_state()`` into an upload of its
+    own and calls ``set_dev``) refreshes the int32 device mirrors
+    ``table_dev``, ``lens_dev`` and ``cap_dev`` that the kernels and
+    ``decode_step_paged`` read. Rows at and past a length, and free pages,
+    hold stale or uninitialised data and are never read."""
+
+    def __init__(self, model, num_seats: int, num_pages: int, page_size: int = 16,
+                 device=None, dtype=None):
+        cfg = model.config
+        page_size = int(page_size)
+        if not 16 <= page_size <= 128 or page_size & (page_size - 1):
+            raise ValueError("PagedKVCache: page_size must be a power of two in "
+                             f"[16, 128], got {page_size}")
+        if cfg.block_size % page_size:
+            raise ValueError(f"PagedKVCache: page_size {page_size} does not divide "
+                             f"block_size {cfg.block_size}")
+        if num_seats < 1 or num_pages < 1:
+            raise ValueError("PagedKVCache: num_seats >= 1 and num_pages >= 1 required")
+        device = model.wte.device if device is None else device
+        dtype = model.wte.dtype if dtype is None else dtype
+        self.block_size = cfg.block_size
+        self.page_size = page_size
+        self.num_pages = int(num_pages)
+        self.max_pages = cfg.block_size // page_size       # MP
+        self.buf = torch.empty(cfg.n_layer, 2, num_pages, cfg.n_head, page_size,
+                               cfg.head_dim, device=device, dtype=dtype)
+        self.k = [self.buf[li, 0] for li in range(cfg.n_layer)]
+        self.v = [self.buf[li, 1] for li in range(cfg.n_layer)]
+        # the kernels take fp32 LN weights: convert once, not per token
+        self.ln_w = [(blk.attn.q_ln_weight.detach().float(),
+                      blk.attn.k_ln_weight.detach().float())
+                     for blk in model.blocks]
+        self.free_pages = list(range(num_pages))            # kept sorted
+        self.pages = [[] for _ in range(num_seats)]
+        self.lens = [0] * num_seats
+        self.cap = [0] * num_seats
+        self.table = torch.full((num_seats, self.max_pages), -1, dtype=torch.int32)
+        self.upload()
+
+    def pages_for(self, n_positions: int) -> int:
+        return -(-int(n_positions) // self.page_size)
+
+    def alloc(self, seat: int, n_positions: int) -> list:
+        """Give the (empty) seat the pages for ``n_positions`` positions, lowest
+        page numbers first; returns them. Host side only."""
+        n = self.pages_for(n_positions)
+        if self.pages[seat]:
+            raise RuntimeError(f"PagedKVCache.alloc: seat {seat} already holds pages")
+        if not 1 <= n <= self.max_pages:
+            raise RuntimeError(f"PagedKVCache.alloc: {n_positions} positions need {n} "
+                               f"pages, 1..{self.max_pages} allowed")
+        if n > len(self.free_pages):
+            raise RuntimeError(f"PagedKVCache.alloc: {n} pages wanted, "
+                               f"{len(self.free_pages)} free")
+        got, self.free_pages = self.free_pages[:n], self.free_pages[n:]
+        self.pages[seat] = got
+        self.cap[seat] = n * self.page_size
+        self.lens[seat] = 0
+        self.table[seat, :n] = torch.tensor(got, dtype=torch.int32)
+        return got
+
+    def free(self, seat: int):
+        """Return the seat's pages to the free list. Host side only."""
+        self.free_pages = sorted(self.free_pages + self.pages[seat])
+        self.pages[seat] = []
+        self.cap[seat] = self.lens[seat] = 0
+        self.table[seat] = -1
+
+    def host_state(self) -> torch.Tensor:
+        """lens | cap | table as one int32 vector, the layout of ``set_dev``."""
+        return torch.cat([torch.tensor(self.lens + self.cap, dtype=torch.int32),
+                          self.table.reshape(-1)])
+
+    def set_dev(self, state_dev: torch.Tensor):
+        """Take the device copy of ``host_state()`` as the mirrors."""
+        S = len(self.lens)
+        self.lens_dev = state_dev[:S]
+        self.cap_dev = state_dev[S:2 * S]
+        self.table_dev = state_dev[2 * S:2 * S + S * self.max_pages].view(S, self.max_pages)
+
+    def upload(self):
+        self.set_dev(self.host_state().to(self.buf.device))
+
+
+@torch.no_grad()
+def decode_step_paged(model, idx_new: torch.Tensor, cache: PagedKVCache, seats,
+                      seats_dev=None) -> torch.Tensor:
+    """``decode_step_slots`` on a ``PagedKVCache``: idx_new (B, Tn), Tn <= 16,
+    with row b at positions cache.lens[seats[b]] .. +Tn-1 of the pages of seat
+    seats[b]; returns the last position's logits (B, V). ``seats`` is B
+    distinct host integers, ``seats_dev`` their int32 device copy (uploaded
+    here when absent). The device mirrors of the cache must be current
+    (``cache.upload``).
+
+    The (B, MP) table rows of the step are gathered from the seat-indexed
+    mirror once, not once per layer. Lengths advance, on the host and on the
+    device, by the retire-when-full rule of ``decode_step_ragged`` with the
+    seat's capacity where that has block_size: a row that is full goes on
+    rewriting the last Tn rows of its own last page and never writes outside
+    its pages."""
+    B, Tn = idx_new.shape
+    seats = [int(s) for s in seats]
+    S = len(cache.lens)
+    if not 1 <= Tn <= 16:
+        raise RuntimeError(f"decode_step_paged: 1 <= Tn <= 16 required, got {Tn}")
+    if len(seats) != B or len(set(seats)) != B or not all(0 <= s < S for s in seats):
+        raise RuntimeError(f"decode_step_paged: {B} distinct seats in [0, {S}) "
+                           f"expected, got {seats}")
+    lens = [cache.lens[s] for s in seats]
+    caps = [cache.cap[s] for s in seats]
+    for n, cap in zip(lens, caps):
+        if cap < Tn or (n < cap and n + Tn > cap):
+            raise RuntimeError(f"decode_step_paged: positions [{n}, {n + Tn}) exceed "
+                               f"the seat's {cap}")
+    if seats_dev is None:
+        seats_dev = torch.tensor(seats, dtype=torch.int32, device=cache.lens_dev.device)
+    pos = [min(n, cap - Tn) for n, cap in zip(lens, caps)]
+    kv_lens = [p + Tn for p in pos]
+    pos_dev = torch.minimum(cache.lens_dev[seats_dev], cache.cap_dev[seats_dev] - Tn)
+    kv_lens_dev = pos_dev + Tn
+    table = cache.table[seats]
+    table_dev = cache.table_dev[seats_dev]
+    sin, cos = model.rope_sin, model.rope_cos
+
+    def attend(li, qkv):
+        qw, kw = cache.ln_w[li]
+        q = ops.kv_append_paged(qkv, qw, kw, sin, cos, cache.k[li], cache.v[li],
+                                pos, table, pos_dev, table_dev)
+        return ops.decode_attention_paged(q, cache.k[li], cache.v[li], kv_lens, table,
+                                          kv_lens_dev, table_dev)
+
+    x, pending = _ragged_layers(model, idx_new, attend)
+    for s, n in zip(seats, kv_lens):
+        cache.lens[s] = n
+    cache.lens_dev[seats_dev] = kv_lens_dev
+    return _ragged_logits(model, x[:, -1:],
+                          None if pending is None else pending[:, -1:])
+
+
+def _prefill_paged(model, cache: PagedKVCache, idx, seat):
+    """Run one prompt idx (1, L) from position 0 into the pages of ``seat``
+    (already allocated) on the paths ``_attend_cached`` takes for a contiguous
+    cache: the flash prefill for L > 16 where the padded prompt fits
+    block_size, 16-row chunks on the paged pair otherwise. The seat's table row
+    and the chunk positions go to the device once, not once per layer.
+    Returns (x, pending) of ``_ragged_layers``."""
+    L = idx.shape[1]
+    dev = cache.buf.device
+    sin, cos = model.rope_sin, model.rope_cos
+    table = cache.table[seat:seat + 1]
+    table_dev = table.to(dev)
+    fits = not idx.is_cuda or -(-L // 128) * 128 <= cache.block_size
+    starts = list(range(0, L, 16))
+    ends = [min(s + 16, L) for s in starts]
+    # ref_backend on the GPU (fp32 pools) takes the chunks, as _prefill_attend does
+    chunked = not (L > 16 and fits) or (cache.buf.is_cuda and not _native_cache(cache))
+    if chunked:
+        marks = torch.tensor(starts + ends, dtype=torch.int32).to(dev)
+
+    def attend(li, qkv):
+        qw, kw = cache.ln_w[li]
+        if not chunked:
+            return ops.prefill_attention_paged(qkv, qw, kw, sin, cos, cache.k[li],
+                                               cache.v[li], table, table_dev)
+        outs = []
+        for i, (s, e) in enumerate(zip(starts, ends)):
+            q = ops.kv_append_paged(qkv[:, s:e], qw, kw, sin, cos, cache.k[li], cache.v[li],
+                                    [s], table, marks[i:i + 1], table_dev)
+            outs.append(ops.decode_attention_paged(
+                q, cache.k[li], cache.v[li], [e], table,
+                marks[len(starts) + i:len(starts) + i + 1], table_dev))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+
+    return _ragged_layers(model, idx, attend)
+
+
 class Request:
     """Handle of one ``DecodeScheduler.submit``: ``done`` once the request has
     left the scheduler, and then ``tokens`` = the prompt plus what it
@@ -551,22 +743,44 @@ class DecodeScheduler:
     request with (seed=s, row=r) reproduces row r of ``generate(..., seed=s)``
     wherever the logits agree. temperature <= 0 is greedy.
 
-    Limits: no paging (a slot is a whole block_size cache) and no sliding
-    window (budget = min(max_new_tokens, block_size - L + 1) as in
-    ``generate_ragged``); admitted prompts are prefilled one at a time, not as
-    a batch, and a prefill is not interleaved with decode steps.
+    With ``num_pages`` the cache is a ``PagedKVCache`` of that many pages of
+    ``page_size`` positions, ``num_slots`` is the number of seats (the largest
+    batch) and a step runs ``decode_step_paged``. A request holds the pages of
+    the positions it can ever write, ceil(min(L + budget - 1, block_size) /
+    page_size) of them, allocated at admission (lowest free page first) and
+    freed at retirement, so the table only changes at a tick and travels in
+    the tick's upload (an admitted request's own table row goes up once more,
+    ahead of it, for its prefill). Admission stays strictly FIFO: the head of
+    the queue is admitted when a seat is free and its pages are; while it does
+    not fit it waits and nothing overtakes it. ``submit`` raises for a request
+    that needs more pages than the pool has. A request's tokens do not depend
+    on ``num_pages``, on ``page_size`` or on which pages it got: the paged
+    kernels have the bits of the slotted ones. ``page_size`` = 16 is a
+    parameter, not a measured optimum. Out of scope: page growth on demand,
+    preemption, prefix sharing, and paging for ``generate`` and
+    ``generate_ragged``.
+
+    Limits: without ``num_pages`` no paging (a slot is a whole block_size
+    cache); no sliding window (budget = min(max_new_tokens, block_size - L +
+    1) as in ``generate_ragged``); admitted prompts are prefilled one at a
+    time, not as a batch, and a prefill is not interleaved with decode steps.
 
     Native under ``native_decode(model)``; otherwise the same code runs on
     ``ops.ref_backend`` with fp32 caches."""
 
-    def __init__(self, model, num_slots: int, tick_every: int = 8):
+    def __init__(self, model, num_slots: int, tick_every: int = 8, *,
+                 num_pages: int | None = None, page_size: int = 16):
         if num_slots < 1 or tick_every < 1:
             raise ValueError("DecodeScheduler: num_slots >= 1 and tick_every >= 1 required")
         model.eval()
         self.model = model
         self.tick_every = int(tick_every)
-        self.cache = KVCache(model, num_slots,
-                             dtype=None if native_decode(model) else torch.float32)
+        dtype = None if native_decode(model) else torch.float32
+        self.paged = num_pages is not None
+        if self.paged:
+            self.cache = PagedKVCache(model, num_slots, num_pages, page_size, dtype=dtype)
+        else:
+            self.cache = KVCache(model, num_slots, dtype=dtype)
         self.queue = collections.deque()
         self.free = list(range(num_slots))
         self.active = []          # requests, in batch-row order
@@ -594,6 +808,13 @@ class DecodeScheduler:
         req = Request(prompt, budget, temperature, top_k, seed, row, eos_id)
         # validates the sampling parameters now, not at admission
         ops.sample_row_params(req.temperature, top_k, [seed], [0], [req.row], 1)
+        if self.paged and budget > 0:
+            # the positions it can ever write: the last token is never fed
+            req._positions = min(L + budget - 1, block)
+            need = self.cache.pages_for(req._positions)
+            if need > self.cache.num_pages:
+                raise RuntimeError(f"DecodeScheduler.submit: the request needs {need} "
+                                   f"pages, the pool has {self.cache.num_pages}")
         if budget == 0:
             req._finish()
             self._finished.append(req)
@@ -613,8 +834,8 @@ class DecodeScheduler:
             self._tick()
         if self.active:
             slots = [r._slot for r in self.active]
-            logits = decode_step_slots(self.model, self._nxt[:, None], self.cache, slots,
-                                       self._slots_dev)
+            step = decode_step_paged if self.paged else decode_step_slots
+            logits = step(self.model, self._nxt[:, None], self.cache, slots, self._slots_dev)
             self._draw(logits)
             self._since_tick += 1
             if self._since_tick >= self.tick_every or \
@@ -648,9 +869,14 @@ class DecodeScheduler:
         model, cache = self.model, self.cache
         idx = req.prompt[-cache.block_size:][None].to(model.wte.device)
         L = idx.shape[1]
-        ks = [k[slot:slot + 1] for k in cache.k]
-        vs = [v[slot:slot + 1] for v in cache.v]
-        x, pending = _ragged_layers(model, idx, _prefill_attend(model, cache, ks, vs, 1, L))
+        if self.paged:
+            cache.alloc(slot, req._positions)
+            x, pending = _prefill_paged(model, cache, idx, slot)
+        else:
+            ks = [k[slot:slot + 1] for k in cache.k]
+            vs = [v[slot:slot + 1] for v in cache.v]
+            x, pending = _ragged_layers(model, idx,
+                                        _prefill_attend(model, cache, ks, vs, 1, L))
         logits = _ragged_logits(model, x[:, -1:],
                                 None if pending is None else pending[:, -1:])
         req._slot = slot
@@ -674,6 +900,8 @@ class DecodeScheduler:
                 if len(req._new) == req.budget or req._new[-1:] == [req.eos_id]:
                     req._finish()
                     self.free.append(req._slot)
+                    if self.paged:
+                        self.cache.free(req._slot)
                     self._finished.append(req)
                 else:
                     keep.append(b)
@@ -681,6 +909,9 @@ class DecodeScheduler:
         firsts = []
         self.free.sort()
         while self.queue and self.free:
+            if self.paged and self.cache.pages_for(self.queue[0]._positions) > \
+                    len(self.cache.free_pages):
+                break             # the head waits for pages; nothing overtakes it
             req = self.queue.popleft()
             firsts.append(self._admit(req, self.free.pop(0)))
             stay.append(req)
@@ -692,6 +923,7 @@ class DecodeScheduler:
             self._nxt, self._cols = None, []
             return
         # one upload: per-slot lengths | slot map | rows kept | sampling parameters
+        # (paged: | per-seat lengths, capacities and block table, at the end)
         S, B = len(self.cache.lens), len(stay)
         host = ops.sample_row_params(
             [r.temperature for r in stay], [r.top_k for r in stay], [r.seed for r in stay],
@@ -699,7 +931,14 @@ class DecodeScheduler:
         meta = torch.tensor(self.cache.lens + [r._slot for r in stay]
                             + keep + list(range(n_old, n_old + len(firsts))),
                             dtype=torch.int32)
-        buf = torch.cat([meta, ops.pack_sample_params(*host).reshape(-1)]).to(dev)
+        parts = [meta, ops.pack_sample_params(*host).reshape(-1)]
+        if self.paged:
+            parts.append(self.cache.host_state())
+        buf = torch.cat(parts).to(dev)
+        if self.paged:
+            n_state = parts[2].numel()
+            self.cache.set_dev(buf[-n_state:])
+            buf = buf[:-n_state]
         self.cache.lens_dev = buf[:S]
         self._slots_dev = buf[S:S + B]
         self._params_dev = buf[S + 2 * B:].view(B, 6)
@@ -712,16 +951,20 @@ class DecodeScheduler:
 def generate_continuous(model, prompts, max_new_tokens: int, temperature: float = 1.0,
                         top_k: int | None = None, eos_id: int | None = None,
                         num_slots: int = 8, tick_every: int = 8,
-                        seed: int | None = None) -> list:
+                        seed: int | None = None, num_pages: int | None = None,
+                        page_size: int = 16) -> list:
     """``generate_ragged`` on a ``DecodeScheduler`` of ``num_slots`` slots:
     every prompt is submitted (prompt i with ``row=i`` and the one ``seed``,
     drawn when None), the scheduler runs until all are done, and the results
     come back in order. There may be more prompts than slots: the rest wait
     for a slot. With a seed, prompt i gets the tokens row i of
-    ``generate(..., seed=seed)`` gets wherever the logits agree."""
+    ``generate(..., seed=seed)`` gets wherever the logits agree. With
+    ``num_pages`` the scheduler's cache is paged (``num_slots`` seats over
+    ``num_pages`` pages of ``page_size`` positions); the tokens are the same."""
     if seed is None:
         seed = ops.draw_sample_seed()
-    sched = DecodeScheduler(model, num_slots, tick_every)
+    sched = DecodeScheduler(model, num_slots, tick_every, num_pages=num_pages,
+                            page_size=page_size)
     handles = [sched.submit(p, max_new_tokens, temperature, top_k, seed=seed, row=i,
                             eos_id=eos_id) for i, p in enumerate(prompts)]
     sched.run()

@@ -36,6 +36,8 @@ SAMPLING_API = ("sample_tokens",)
 # Slot-mapped decode and per-row sampling (continuous batching), under the
 # same rule.
 SLOT_API = ("kv_append_slots", "attn_decode_slots", "sample_tokens_rows")
+# Paged decode (block-table caches), under the same rule.
+PAGED_API = ("kv_append_paged", "attn_decode_paged", "kv_store_paged")
 
 
 def _try_load_ext():
@@ -513,6 +515,122 @@ def prefill_attention(qkv, q_ln_weight, k_ln_weight, sin, cos, k_cache, v_cache,
     o, _ = _C.attn_fwd_packed(q, k, v)          # (B,Tp,H,C)
     k_cache[:, :, :Tn].copy_(k[:, :, :Tn])
     v_cache[:, :, :Tn].copy_(v[:, :, :Tn])
+    return o[:, :Tn].reshape(B, Tn, H * C)
+
+
+# Paged decode: the caches are pools (P,H,PS,C) of P pages of PS positions (a
+# power of two in [16, 128]) and position p of batch row b lives at row p % PS
+# of page block_table[b][p // PS]; MP*PS stands where Tmax stands above and
+# unassigned entries are -1. ``block_table`` (host: nested ints or a CPU
+# integer tensor (B,MP)) is the truth and is validated by the backend: every
+# entry that covers the positions a call touches lies in [0, P), and the pages
+# that receive writes are distinct (attention may name one page in several
+# rows). ``block_table_dev`` is the optional int32 GPU copy, under the same
+# contract as ``pos_dev``. Row b has the bits of the ragged op on the cache
+# gathered through the table.
+def _host_table(table, B, who):
+    t = table if isinstance(table, torch.Tensor) else torch.tensor(table)
+    if t.is_cuda or t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1 \
+            or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise RuntimeError(f"{who}: expected a ({B}, MP) integer block table on the "
+                           f"host, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    return t.to(torch.int64)
+
+
+def _check_pools(k_pool, v_pool, H, C, who):
+    if k_pool.dim() != 4 or k_pool.shape != v_pool.shape or \
+            (k_pool.shape[1], k_pool.shape[3]) != (H, C):
+        raise RuntimeError(f"{who}: the pools must be (P,{H},PS,{C}), got "
+                           f"{tuple(k_pool.shape)} and {tuple(v_pool.shape)}")
+
+
+def kv_append_paged(qkv, q_ln_weight, k_ln_weight, sin, cos, k_pool, v_pool,
+                    pos, block_table, pos_dev=None, block_table_dev=None,
+                    eps: float = 1e-6):
+    """``kv_append_ragged`` into paged pools: qkv (B,Tn,3,H,C), pools
+    (P,H,PS,C). Writes positions [pos[b], pos[b]+Tn) of sequence b into the
+    pages its table row names and nothing else; returns q (B,H,Tn,C)."""
+    who = "kv_append_paged"
+    B, Tn, three, H, C = qkv.shape
+    if three != 3 or Tn < 1:
+        raise RuntimeError(f"{who}: qkv must be (B,Tn,3,H,C) with Tn >= 1")
+    pos = _host_lens(pos, B, who)
+    table = _host_table(block_table, B, who)
+    _check_pools(k_pool, v_pool, H, C, who)
+    return _ragged_backend(qkv, k_pool).kv_append_paged(
+        qkv.contiguous(), q_ln_weight, k_ln_weight, sin, cos, k_pool, v_pool,
+        _dev_lens(pos, pos_dev, qkv), pos, _dev_lens(table, block_table_dev, qkv), table,
+        eps)
+
+
+def decode_attention_paged(q, k_pool, v_pool, kv_lens, block_table, kv_lens_dev=None,
+                           block_table_dev=None, num_splits: int = 0):
+    """``decode_attention_ragged`` on paged pools: sequence b holds kv_lens[b]
+    positions in the pages of its table row. Returns o (B,Tq,H*C).
+    ``num_splits`` = 0 applies the uniform rule to the longest sequence, as
+    the ragged op does."""
+    who = "decode_attention_paged"
+    B, H, Tq, C = q.shape
+    kv_lens = _host_lens(kv_lens, B, who)
+    table = _host_table(block_table, B, who)
+    _check_pools(k_pool, v_pool, H, C, who)
+    return _ragged_backend(q, k_pool).attn_decode_paged(
+        q.contiguous(), k_pool, v_pool, _dev_lens(kv_lens, kv_lens_dev, q), kv_lens,
+        _dev_lens(table, block_table_dev, q), table, int(num_splits)).view(B, Tq, H * C)
+
+
+def kv_store_paged(k, v, k_pool, v_pool, lens, block_table, block_table_dev=None):
+    """Rows [0, lens[b]) of contiguous k, v (B,H,T,C) into the pages of
+    sequence b's table row, in place; nothing else is written."""
+    who = "kv_store_paged"
+    B, H, T, C = k.shape
+    lens = _host_lens(lens, B, who)
+    table = _host_table(block_table, B, who)
+    _check_pools(k_pool, v_pool, H, C, who)
+    _ragged_backend(k, k_pool).kv_store_paged(
+        k.contiguous(), v.contiguous(), k_pool, v_pool, _dev_lens(lens, None, k), lens,
+        _dev_lens(table, block_table_dev, k), table)
+
+
+def prefill_attention_paged(qkv, q_ln_weight, k_ln_weight, sin, cos, k_pool, v_pool,
+                            block_table, block_table_dev=None, eps: float = 1e-6):
+    """``prefill_attention`` into paged pools: whole prompts at position 0,
+    qkv (B,Tn,3,H,C) -> o (B,Tn,H*C), with positions [0, Tn) of every sequence
+    written into the pages of its table row. On GPU: the same qkv_prep_fwd +
+    attn_fwd_packed on the prompt padded to a multiple of 128 rows, then
+    ``kv_store_paged`` of rows [0, Tn) where the contiguous caches take a
+    copy. On ref_backend (the CPU, fp32 pools): the paged append, then
+    attn_decode's math on the gathered cache without its 16-row limit."""
+    who = "prefill_attention_paged"
+    B, Tn, _, H, C = qkv.shape
+    table = _host_table(block_table, B, who)
+    _check_pools(k_pool, v_pool, H, C, who)
+    PS = k_pool.shape[2]
+    if Tn > table.shape[1] * PS:
+        raise RuntimeError(f"{who}: {Tn} rows do not fit the table's {table.shape[1] * PS}")
+    if _ragged_backend(qkv, k_pool) is ref_backend:
+        q = kv_append_paged(qkv, q_ln_weight, k_ln_weight, sin, cos, k_pool, v_pool,
+                            [0] * B, table, None, block_table_dev, eps)
+        return torch.cat([ref_backend._decode_attention_ref(
+            q[b:b + 1], ref_backend._gather_pages(k_pool, table, b, Tn, PS),
+            ref_backend._gather_pages(v_pool, table, b, Tn, PS), Tn)
+            for b in range(B)], dim=0).view(B, Tn, H * C)
+    if sin.shape[0] < Tn or cos.shape[0] < Tn:
+        raise RuntimeError(f"{who}: sin/cos tables have {sin.shape[0]} rows, "
+                           f"position {Tn - 1} needed")
+    Tp = -(-Tn // 128) * 128
+    pad = Tp - Tn
+    if pad:
+        qkv = torch.nn.functional.pad(qkv, (0, 0, 0, 0, 0, 0, 0, pad))
+    sin, cos = sin[:Tp], cos[:Tp]
+    if sin.shape[0] < Tp:  # tables end inside the padding: any finite row does
+        extra = (0, 0, 0, Tp - sin.shape[0])
+        sin = torch.nn.functional.pad(sin, extra)
+        cos = torch.nn.functional.pad(cos, extra)
+    q, k, v, _, _ = _C.qkv_prep_fwd(qkv.contiguous(), q_ln_weight, k_ln_weight,
+                                    sin, cos, eps)
+    o, _ = _C.attn_fwd_packed(q, k, v)          # (B,Tp,H,C)
+    kv_store_paged(k, v, k_pool, v_pool, [Tn] * B, table, block_table_dev)
     return o[:, :Tn].reshape(B, Tn, H * C)
 
 

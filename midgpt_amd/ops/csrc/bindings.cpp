@@ -9,6 +9,7 @@
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 
+#include <algorithm>
 #include <climits>
 #include <type_traits>
 #include <vector>
@@ -740,22 +741,86 @@ static SlotMap slot_map(const Call& c, const torch::Tensor& slots_dev,
   return m;
 }
 
+// The block table of a paged call: the caches are pools (P,H,PS,C) of P pages
+// of PS positions (a power of two in [16, 128]) and position p of batch row b
+// lives at row p % PS of page table[b][p / PS]; MP*PS stands where Tmax stands
+// elsewhere. Host copy, a CPU integer tensor (B,MP): the truth, validated by
+// cover(); the (B,MP) int32 device copy is what the kernels read, and the
+// caller keeps the two equal.
+struct PageTable {
+  torch::Tensor host64;        // keeps `host` alive
+  const int64_t* host = nullptr;  // (B, MP), row-major
+  const int* dev = nullptr;    // null: not a paged call
+  int B = 0, P = 0, MP = 0, PS = 0, shift = 0;
+  std::vector<int64_t> written;  // pages that receive writes, over the whole call
+
+  int64_t tmax() const { return (int64_t)MP * PS; }
+  // Every entry that covers positions [lo, hi) of row b lies in [0, P); with
+  // `write`, no page is named by two of the entries that receive writes (two
+  // rows, or two blocks of one row, would race on it): check_writes() after
+  // the last row.
+  void cover(const Call& c, int b, int64_t lo, int64_t hi, bool write) {
+    for (int64_t j = lo / PS; j * PS < hi; ++j) {
+      const int64_t pg = host[(size_t)b * MP + j];
+      TORCH_CHECK(pg >= 0 && pg < P, c.who, ": block_table[", b, "][", j, "] = ", pg,
+                  " is outside the pool of ", P, " pages");
+      if (write) written.push_back(pg);
+    }
+  }
+  void check_writes(const Call& c) {
+    std::sort(written.begin(), written.end());
+    const auto dup = std::adjacent_find(written.begin(), written.end());
+    TORCH_CHECK(dup == written.end(), c.who, ": page ", dup == written.end() ? -1 : *dup,
+                " receives writes twice");
+  }
+};
+static PageTable page_table(const Call& c, const torch::Tensor& table_dev,
+                            const torch::Tensor& table_host, const torch::Tensor& k_pool,
+                            const torch::Tensor& v_pool, int B, int H, int C, u16** kp,
+                            u16** vp) {
+  PageTable t;
+  TORCH_CHECK(C == 64 || C == 128, c.who, ": head dim 64 or 128 (got ", C, ")");
+  *kp = c.bf16_out(k_pool, "k_pool", {ANY, H, ANY, C});
+  *vp = c.bf16_out(v_pool, "v_pool", k_pool.sizes());
+  t.B = B;
+  t.P = c.dim(k_pool, 0);
+  t.PS = c.dim(k_pool, 2);
+  TORCH_CHECK(t.PS >= 16 && t.PS <= 128 && (t.PS & (t.PS - 1)) == 0, c.who,
+              ": the page size must be a power of two in [16, 128], got ", t.PS);
+  while ((1 << t.shift) < t.PS) ++t.shift;
+  TORCH_CHECK(!table_host.is_cuda() && table_host.dim() == 2 && table_host.size(0) == B &&
+              table_host.size(1) >= 1 && at::isIntegralType(table_host.scalar_type(), false),
+              c.who, ": the host block table must be a CPU integer tensor (", B, ", MP)");
+  t.MP = c.dim(table_host, 1);
+  TORCH_CHECK(t.tmax() <= INT_MAX, c.who, ": MP*PS does not fit int");
+  t.host64 = table_host.to(torch::kLong).contiguous();  // no copy for what ops passes
+  t.host = t.host64.data_ptr<int64_t>();
+  t.dev = c.i32(table_dev, "block_table_dev", {B, t.MP});
+  return t;
+}
+
 // sin/cos are the FULL tables (rows >= pos+Tn, C/2) fp32; fp32 LN weights are
 // used in place, others converted. pos_dev == nullptr: every sequence at
 // pos[0]; otherwise sequence b at pos[b] (host) == pos_dev[b] (device).
 // slots: sequence b in cache slot slots[b] of a pool (ragged calls only);
-// null: in cache row b.
+// null: in cache row b. table (ragged calls only, not with slots): the caches
+// are paged pools and sequence b's rows are found through its block table.
 static torch::Tensor kv_append_impl(const Call& c, torch::Tensor qkv, torch::Tensor qw,
                                     torch::Tensor kw, torch::Tensor sin_t, torch::Tensor cos_t,
                                     torch::Tensor k_cache, torch::Tensor v_cache,
                                     const std::vector<int64_t>& pos, const int* pos_dev,
                                     double eps, const torch::Tensor* slots_dev = nullptr,
-                                    const torch::Tensor* slots_host = nullptr) {
+                                    const torch::Tensor* slots_host = nullptr,
+                                    const torch::Tensor* table_dev = nullptr,
+                                    const torch::Tensor* table_host = nullptr) {
   const u16* qkvp = c.bf16(qkv, "qkv", {ANY, ANY, 3, ANY, ANY});
   int B = c.dim(qkv, 0), Tn = c.dim(qkv, 1), H = c.dim(qkv, 3), C = c.dim(qkv, 4);
   u16 *kcp, *vcp;
   int S = 0;
-  const int64_t Tmax =
+  PageTable table;
+  if (table_dev) table = page_table(c, *table_dev, *table_host, k_cache, v_cache, B, H, C,
+                                    &kcp, &vcp);
+  const int64_t Tmax = table_dev ? table.tmax() :
       decode_caches(c, k_cache, v_cache, B, H, C, &kcp, &vcp, slots_dev ? &S : nullptr);
   SlotMap slots;
   if (slots_dev) slots = slot_map(c, *slots_dev, *slots_host, B, S);
@@ -773,17 +838,24 @@ static torch::Tensor kv_append_impl(const Call& c, torch::Tensor qkv, torch::Ten
     TORCH_CHECK(sin_t.size(0) >= p + Tn, "kv_append: sin/cos tables have ", sin_t.size(0),
                 " rows, position ", p + Tn - 1, " needed");
   }
+  if (table.dev) {
+    for (int b = 0; b < B; ++b) table.cover(c, b, pos[b], pos[b] + Tn, true);
+    table.check_writes(c);
+  }
   auto q = torch::empty({B, H, Tn, C}, qkv.options());
   const long nrows = (long)B * Tn * H * 3;
   const int rpb = 4 * (WAVE / (C / 8));  // rows per 256-thread block
   const long grid = std::min((nrows + rpb - 1) / rpb, (long)16384);
   dispatch_flag(pos_dev != nullptr, [&](auto ragged) {
     dispatch_flag(slots.dev != nullptr, [&](auto slotted) {
-      constexpr bool RAGGED = decltype(ragged)::value, SLOTS = decltype(slotted)::value;
-      if constexpr (RAGGED || !SLOTS)
-        launch(kv_append_kernel<RAGGED, SLOTS>, grid, 256, 0, qkvp, qwp, kwp, sinp, cosp,
-               fresh<u16>(q), kcp, vcp, B, Tn, H, C, (long)Tmax, (long)pos[0], pos_dev,
-               (float)eps, slots.dev, slots.S);
+      dispatch_flag(table.dev != nullptr, [&](auto paged) {
+        constexpr bool RAGGED = decltype(ragged)::value, SLOTS = decltype(slotted)::value,
+                       PAGED = decltype(paged)::value;
+        if constexpr ((RAGGED || !SLOTS) && (!PAGED || (RAGGED && !SLOTS)))
+          launch(kv_append_kernel<RAGGED, SLOTS, PAGED>, grid, 256, 0, qkvp, qwp, kwp, sinp,
+                 cosp, fresh<u16>(q), kcp, vcp, B, Tn, H, C, (long)Tmax, (long)pos[0], pos_dev,
+                 (float)eps, slots.dev, slots.S, table.dev, table.P, table.MP, table.shift);
+      });
     });
   });
   return q;
@@ -822,6 +894,48 @@ torch::Tensor kv_append_slots(torch::Tensor qkv, torch::Tensor qw, torch::Tensor
   auto pos = host_lens(pos_host, B, c.who);
   return kv_append_impl(c, qkv, qw, kw, sin_t, cos_t, k_cache, v_cache, pos,
                         c.i32(pos_dev, "pos_dev", {B}), eps, &slots_dev, &slots_host);
+}
+
+torch::Tensor kv_append_paged(torch::Tensor qkv, torch::Tensor qw, torch::Tensor kw,
+                              torch::Tensor sin_t, torch::Tensor cos_t,
+                              torch::Tensor k_pool, torch::Tensor v_pool,
+                              torch::Tensor pos_dev, torch::Tensor pos_host,
+                              torch::Tensor table_dev, torch::Tensor table_host, double eps) {
+  Call c("kv_append_paged", qkv);
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(0) >= 1,
+              "kv_append: qkv must be (B,Tn,3,H,C) with B >= 1");
+  const int B = c.dim(qkv, 0);
+  auto pos = host_lens(pos_host, B, c.who);
+  return kv_append_impl(c, qkv, qw, kw, sin_t, cos_t, k_pool, v_pool, pos,
+                        c.i32(pos_dev, "pos_dev", {B}), eps, nullptr, nullptr, &table_dev,
+                        &table_host);
+}
+
+// Rows [0, lens[b]) of contiguous k, v (B,H,T,C) into the pages that the block
+// table names (decode.hip); lens like the positions above: host copy validated,
+// (B,) int32 device copy read by the kernel.
+void kv_store_paged(torch::Tensor k, torch::Tensor v, torch::Tensor k_pool,
+                    torch::Tensor v_pool, torch::Tensor lens_dev, torch::Tensor lens_host,
+                    torch::Tensor table_dev, torch::Tensor table_host) {
+  Call c("kv_store_paged", k);
+  const u16* kp = c.bf16(k, "k", {ANY, ANY, ANY, ANY});
+  const u16* vp = c.bf16(v, "v", k.sizes());
+  const int B = c.dim(k, 0), H = c.dim(k, 1), T = c.dim(k, 2), C = c.dim(k, 3);
+  TORCH_CHECK(B >= 1, c.who, ": k must be (B,H,T,C) with B >= 1");
+  u16 *kpp, *vpp;
+  PageTable table = page_table(c, table_dev, table_host, k_pool, v_pool, B, H, C, &kpp, &vpp);
+  auto lens = host_lens(lens_host, B, c.who);
+  const int* lp = c.i32(lens_dev, "lens_dev", {B});
+  for (int b = 0; b < B; ++b) {
+    TORCH_CHECK(lens[b] >= 0 && lens[b] <= T && lens[b] <= table.tmax(), c.who, ": length ",
+                lens[b], " exceeds the ", T, " rows given or the table's ", table.tmax());
+    table.cover(c, b, 0, lens[b], true);
+  }
+  table.check_writes(c);
+  const long nunits = (long)B * H * T * (C / 8);
+  const long grid = std::min((nunits + 255) / 256, (long)16384);
+  launch(kv_store_paged_kernel, grid, 256, 0, kp, vp, kpp, vpp, lp, table.dev, B, H, T, C,
+         table.P, table.MP, table.shift);
 }
 
 static int decode_cu_count() {
@@ -863,12 +977,17 @@ static torch::Tensor attn_decode_impl(const Call& c, torch::Tensor q, torch::Ten
                                       const std::vector<int64_t>& kv_lens,
                                       const int* lens_dev, int64_t num_splits,
                                       const torch::Tensor* slots_dev = nullptr,
-                                      const torch::Tensor* slots_host = nullptr) {
+                                      const torch::Tensor* slots_host = nullptr,
+                                      const torch::Tensor* table_dev = nullptr,
+                                      const torch::Tensor* table_host = nullptr) {
   const u16* qp = c.bf16(q, "q", {ANY, ANY, ANY, ANY});
   int B = c.dim(q, 0), H = c.dim(q, 1), Tq = c.dim(q, 2), C = c.dim(q, 3);
   u16 *kcp, *vcp;
   int pool = 0;
-  const int64_t Tmax =
+  PageTable table;
+  if (table_dev) table = page_table(c, *table_dev, *table_host, k_cache, v_cache, B, H, C,
+                                    &kcp, &vcp);
+  const int64_t Tmax = table_dev ? table.tmax() :
       decode_caches(c, k_cache, v_cache, B, H, C, &kcp, &vcp, slots_dev ? &pool : nullptr);
   SlotMap slots;
   if (slots_dev) slots = slot_map(c, *slots_dev, *slots_host, B, pool);
@@ -880,6 +999,8 @@ static torch::Tensor attn_decode_impl(const Call& c, torch::Tensor q, torch::Ten
                 kv_len, ")");
     kv_max = std::max(kv_max, kv_len);
   }
+  if (table.dev)  // reads only: a page may be shared by several rows
+    for (int b = 0; b < B; ++b) table.cover(c, b, 0, kv_lens[b], false);
   TORCH_CHECK(num_splits >= 0 && num_splits <= DECODE_MAX_SPLITS,
               "attn_decode: num_splits must be in [0, ", DECODE_MAX_SPLITS, "]");
   const long rows = (long)B * H * Tq;
@@ -901,11 +1022,15 @@ static torch::Tensor attn_decode_impl(const Call& c, torch::Tensor q, torch::Ten
   dispatch_int<128, 64>(C, [&](auto cc) {
     dispatch_flag(lens_dev != nullptr, [&](auto ragged) {
       dispatch_flag(slots.dev != nullptr, [&](auto slotted) {
-        constexpr bool RAGGED = decltype(ragged)::value, SLOTS = decltype(slotted)::value;
-        if constexpr (RAGGED || !SLOTS)
-          launch(attn_decode_kernel<decltype(cc)::value, RAGGED, SLOTS>, dim3(rows, S), 256, 0,
-                 qp, kcp, vcp, fresh<u16>(o), accp, mlp, H, Tq, (long)Tmax, (int)kv_lens[0],
-                 lens_dev, S, scale, slots.dev, slots.S);
+        dispatch_flag(table.dev != nullptr, [&](auto paged) {
+          constexpr bool RAGGED = decltype(ragged)::value, SLOTS = decltype(slotted)::value,
+                         PAGED = decltype(paged)::value;
+          if constexpr ((RAGGED || !SLOTS) && (!PAGED || (RAGGED && !SLOTS)))
+            launch(attn_decode_kernel<decltype(cc)::value, RAGGED, SLOTS, PAGED>, dim3(rows, S),
+                   256, 0, qp, kcp, vcp, fresh<u16>(o), accp, mlp, H, Tq, (long)Tmax,
+                   (int)kv_lens[0], lens_dev, S, scale, slots.dev, slots.S, table.dev, table.P,
+                   table.MP, table.shift);
+        });
       });
     });
   });
@@ -942,6 +1067,19 @@ torch::Tensor attn_decode_slots(torch::Tensor q, torch::Tensor k_cache, torch::T
   return attn_decode_impl(c, q, k_cache, v_cache, lens,
                           c.i32(kv_lens_dev, "kv_lens_dev", {B}), num_splits, &slots_dev,
                           &slots_host);
+}
+
+torch::Tensor attn_decode_paged(torch::Tensor q, torch::Tensor k_pool, torch::Tensor v_pool,
+                                torch::Tensor kv_lens_dev, torch::Tensor kv_lens_host,
+                                torch::Tensor table_dev, torch::Tensor table_host,
+                                int64_t num_splits) {
+  Call c("attn_decode_paged", q);
+  TORCH_CHECK(q.dim() == 4 && q.size(0) >= 1, "attn_decode: q must be (B,H,Tq,C) with B >= 1");
+  const int B = c.dim(q, 0);
+  auto lens = host_lens(kv_lens_host, B, c.who);
+  return attn_decode_impl(c, q, k_pool, v_pool, lens,
+                          c.i32(kv_lens_dev, "kv_lens_dev", {B}), num_splits, nullptr, nullptr,
+                          &table_dev, &table_host);
 }
 
 // ---------------------------------------------------------------------------
@@ -1067,6 +1205,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("attn_decode_slots", &attn_decode_slots, py::arg("q"), py::arg("k_cache"),
           py::arg("v_cache"), py::arg("kv_lens_dev"), py::arg("kv_lens_host"),
           py::arg("slots_dev"), py::arg("slots_host"), py::arg("num_splits") = 0);
+  mod.def("kv_append_paged", &kv_append_paged, py::arg("qkv"), py::arg("qw"), py::arg("kw"),
+          py::arg("sin"), py::arg("cos"), py::arg("k_pool"), py::arg("v_pool"),
+          py::arg("pos_dev"), py::arg("pos_host"), py::arg("block_table_dev"),
+          py::arg("block_table_host"), py::arg("eps") = 1e-6);
+  mod.def("attn_decode_paged", &attn_decode_paged, py::arg("q"), py::arg("k_pool"),
+          py::arg("v_pool"), py::arg("kv_lens_dev"), py::arg("kv_lens_host"),
+          py::arg("block_table_dev"), py::arg("block_table_host"), py::arg("num_splits") = 0);
+  mod.def("kv_store_paged", &kv_store_paged, py::arg("k"), py::arg("v"), py::arg("k_pool"),
+          py::arg("v_pool"), py::arg("lens_dev"), py::arg("lens_host"),
+          py::arg("block_table_dev"), py::arg("block_table_host"));
   mod.def("attn_decode_auto_splits", &attn_decode_auto_splits, py::arg("rows"),
           py::arg("kv_len"), py::arg("cus"));
   mod.def("sample_tokens", &sample_tokens, py::arg("logits"), py::arg("inv_t"),

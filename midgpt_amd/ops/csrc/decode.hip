@@ -5,6 +5,7 @@
 //                        straight into the (B,H,Tmax,C) caches.
 //   attn_decode_kernel   Tq <= 16 query rows against the cache, split-KV.
 //   attn_decode_combine_kernel   merges the per-slice partials.
+//   kv_store_paged_kernel   contiguous (B,H,T,C) K/V rows into a paged pool.
 //
 // The first two have a RAGGED instantiation that reads the position / length
 // of sequence b from an int32 array instead of one value for the batch: the
@@ -17,6 +18,14 @@
 // (slots[b]*H + h)*Tmax*C instead of (b*H + h)*Tmax*C. One more 4-byte load
 // per row / block and nothing else: row b of a slotted call has the bits of
 // the ragged call on the gathered cache[slots].
+//
+// PAGED (implies RAGGED, exclusive with SLOTS) takes that indirection per
+// block of keys: the caches are pools of P pages, (P,H,PS,C) with PS a power of
+// two, and position p of sequence b lives at row p % PS of page
+// block_table[b][p / PS] of a (B,MP) int32 table; MP*PS plays the role of Tmax.
+// Only the address of a cache row changes, so row b of a paged call has the
+// bits of the ragged call on the cache gathered through the table.
+// kv_store_paged_kernel copies contiguous K/V rows into the pages (prefill).
 //
 // Decode attention is a memory-bound stream over K and V with one query row
 // per head: no MFMA, no LDS staging. K/V rows go straight to VGPRs with
@@ -31,7 +40,11 @@
 // SLOTS: the cache rows are those of slot slots[b] of S. The binding validated
 // the host copy of the map; a device copy that names a slot outside [0, S)
 // writes nothing for that row (neither cache nor q).
-template <bool RAGGED, bool SLOTS = false>
+// PAGED: the caches are (P,H,PS,C) pools with PS = 1 << ps_shift and Tmax =
+// MP*PS; row pos + t goes to the page block_table[b][(pos + t) >> ps_shift].
+// An entry outside [0, P) (a device table that disagrees with the validated
+// host copy) writes nothing for that row, neither cache nor q.
+template <bool RAGGED, bool SLOTS = false, bool PAGED = false>
 __global__ void kv_append_kernel(const u16* __restrict__ qkv,
                                  const float* __restrict__ qw,
                                  const float* __restrict__ kw,
@@ -41,8 +54,11 @@ __global__ void kv_append_kernel(const u16* __restrict__ qkv,
                                  u16* __restrict__ v_cache,
                                  int B, int Tn, int H, int C, long Tmax, long pos,
                                  const int* __restrict__ pos_b, float eps,
-                                 const int* __restrict__ slots, int S) {
+                                 const int* __restrict__ slots, int S,
+                                 const int* __restrict__ block_table, int P,
+                                 int MP, int ps_shift) {
   static_assert(RAGGED || !SLOTS, "SLOTS implies RAGGED");
+  static_assert(!PAGED || (RAGGED && !SLOTS), "PAGED implies RAGGED, excludes SLOTS");
   const int LPR = C / 8;                 // lanes per row (8 or 16)
   const int RPW = WAVE / LPR;            // rows per wave
   const int sub = lane_id() % LPR;
@@ -68,8 +84,16 @@ __global__ void kv_append_kernel(const u16* __restrict__ qkv,
       cb = slots[b];
       if (cb < 0 || cb >= S) continue;
     }
+    long crow = pos + t;                 // row inside the cache of (cb, h)
+    long cstride = Tmax;                 // rows per (cb, h)
+    if constexpr (PAGED) {
+      cb = block_table[b * MP + (crow >> ps_shift)];
+      if (cb < 0 || cb >= P) continue;
+      cstride = 1L << ps_shift;
+      crow &= cstride - 1;
+    }
     const u16x8 raw = *(const u16x8*)(qkv + ((bt * 3 + role) * H + h) * C + sub * 8);
-    const long cache_off = ((cb * H + h) * Tmax + pos + t) * C + sub * 8;
+    const long cache_off = ((cb * H + h) * cstride + crow) * C + sub * 8;
     if (role == 2) {
       *(u16x8*)(v_cache + cache_off) = raw;
       continue;
@@ -106,7 +130,13 @@ DEVINL float decode_weight(float m, float m_ref) {
 // truth; for a device copy that names a slot outside [0, S) the block treats
 // its row as kv_len = Tq in slot 0: it reads rows [0, Tq) of a cache that
 // exists, never anything outside it, and slice 0 still writes its output or
-// partials (whatever those rows hold).
+// partials (whatever those rows hold). PAGED: key k of sequence b is row
+// k % PS of page block_table[b][k / PS] of a (P,H,PS,C) pool, Tmax = MP*PS.
+// The table entries of a batch of U keys are loaded ahead of its K/V loads,
+// one batch early, so a batch still has 2*U 16-byte loads in flight and an
+// iteration does not wait for two dependent loads. For an entry outside [0, P)
+// (a device table that disagrees with the host copy) the key is read from
+// page 0: in bounds, the values unspecified.
 //
 // 256 threads form G = 256/(C/8) lane groups; group g takes keys k0+g,
 // k0+g+G, ... in batches of U keys whose K and V loads (2*U 16-byte loads per
@@ -115,14 +145,16 @@ DEVINL float decode_weight(float m, float m_ref) {
 // and its own 8 columns of acc. Groups merge by shuffles, waves through LDS.
 // num_splits == 1: writes o (B,Tq,H,C) bf16. Otherwise writes the slice's
 // fp32 (m, l) to ws_ml[row][split][2] and acc to ws_acc[row][split][C].
-template <int C, bool RAGGED, bool SLOTS = false>
+template <int C, bool RAGGED, bool SLOTS = false, bool PAGED = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k_cache,
     const u16* __restrict__ v_cache, u16* __restrict__ o,
     float* __restrict__ ws_acc, float* __restrict__ ws_ml,
     int H, int Tq, long Tmax, int kv_len, const int* __restrict__ kv_lens,
-    int num_splits, float scale, const int* __restrict__ slots, int S) {
+    int num_splits, float scale, const int* __restrict__ slots, int S,
+    const int* __restrict__ block_table, int P, int MP, int ps_shift) {
   static_assert(RAGGED || !SLOTS, "SLOTS implies RAGGED");
+  static_assert(!PAGED || (RAGGED && !SLOTS), "PAGED implies RAGGED, excludes SLOTS");
   constexpr int LPR = C / 8;
   constexpr int G = 256 / LPR;
   constexpr int U = 4;
@@ -141,6 +173,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
     // takes 15 more VGPRs (profiles/decode.md)
     kv_len = ok ? min(kv_lens[bh / H], (int)Tmax) : Tq;
     cbh = (ok ? slot : 0) * H + bh % H;
+  } else if constexpr (PAGED) {
+    // max: nor must it make a slice start below key 0 (Tq <= Tmax on the host)
+    kv_len = max(Tq, min(kv_lens[bh / H], (int)Tmax));
   } else if constexpr (RAGGED) {
     kv_len = min(kv_lens[bh / H], (int)Tmax);
   }
@@ -150,8 +185,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
   const int k1 = min(limit, k0 + per);
   const int sub = threadIdx.x % LPR;
   const int g = threadIdx.x / LPR;
-  const u16* kb = k_cache + (long)cbh * Tmax * C + sub * 8;
-  const u16* vb = v_cache + (long)cbh * Tmax * C + sub * 8;
+  // PAGED: the page is part of the row offset, not of the base
+  const u16* kb = k_cache + (PAGED ? 0 : (long)cbh * Tmax * C) + sub * 8;
+  const u16* vb = v_cache + (PAGED ? 0 : (long)cbh * Tmax * C) + sub * 8;
+  const int* tb = PAGED ? block_table + (long)(bh / H) * MP : nullptr;
 
   float qf[8];
   {
@@ -166,9 +203,27 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
 
   // The first key of a batch (kk) is always inside the slice, so every batch
   // has a finite maximum.
+  // PAGED: the table entries of a batch, loaded while the batch before it is
+  // in flight, so that an iteration waits for one memory latency, not two.
+  [[maybe_unused]] int page[U];
+  if constexpr (PAGED) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int key = k0 + g + u * G;
+      page[u] = key < k1 ? tb[key >> ps_shift] : 0;
+    }
+  }
   for (int kk = k0 + g; kk < k1; kk += G * U) {
     u16x8 kr[U], vr[U];
     bool ok[U];
+    [[maybe_unused]] int page_next[U];
+    if constexpr (PAGED) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long key = (long)kk + G * U + u * G;
+        page_next[u] = key < k1 ? tb[key >> ps_shift] : 0;
+      }
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int key = kk + u * G;
@@ -176,8 +231,13 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
       kr[u] = 0;
       vr[u] = 0;
       if (ok[u]) {
-        kr[u] = *(const u16x8*)(kb + (long)key * C);
-        vr[u] = *(const u16x8*)(vb + (long)key * C);
+        long crow = key;                 // row of the key from kb / vb
+        if constexpr (PAGED) {
+          const long pg = (unsigned)page[u] < (unsigned)P ? page[u] : 0;
+          crow = ((pg * H + bh % H) << ps_shift) + (key & ((1 << ps_shift) - 1));
+        }
+        kr[u] = *(const u16x8*)(kb + crow * C);
+        vr[u] = *(const u16x8*)(vb + crow * C);
       }
     }
     float s[U];
@@ -204,6 +264,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(
       for (int j = 0; j < 8; ++j) acc[j] += p * b2f(vr[u][j]);
     }
     m = mn;
+    if constexpr (PAGED) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) page[u] = page_next[u];
+    }
   }
 
   // merge the lane groups of a wave
@@ -279,4 +343,35 @@ __global__ void attn_decode_combine_kernel(const float* __restrict__ ws_acc,
   const int i = row % Tq, bh = row / Tq;
   const int b = bh / H, h = bh % H;
   o[(((long)b * Tq + i) * H + h) * C + c] = f2b(A / L);
+}
+
+// Rows [0, lens[b]) of contiguous k, v (B,H,T,C) into the pages block_table
+// names: row t of sequence b goes to row t % PS of page block_table[b][t / PS]
+// of the (P,H,PS,C) pools. One 16-byte unit of K and of V per lane and
+// iteration, grid-stride; nothing else is written. A device length above
+// min(T, MP*PS) is cut to it and a table entry outside [0, P) writes nothing:
+// no access leaves the pools (the binding validated the host copies).
+__global__ void kv_store_paged_kernel(const u16* __restrict__ k,
+                                      const u16* __restrict__ v,
+                                      u16* __restrict__ k_pool, u16* __restrict__ v_pool,
+                                      const int* __restrict__ lens,
+                                      const int* __restrict__ block_table, int B, int H,
+                                      int T, int C, int P, int MP, int ps_shift) {
+  const int LPR = C / 8;
+  const long nunits = (long)B * H * T * LPR;
+  const long step = (long)gridDim.x * blockDim.x;
+  const long tcap = min((long)T, (long)MP << ps_shift);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nunits; i += step) {
+    const int sub = (int)(i % LPR);
+    const long row = i / LPR;            // (b*H + h)*T + t
+    const long t = row % T;
+    const long bh = row / T;
+    const long h = bh % H, b = bh / H;
+    if (t >= min((long)lens[b], tcap)) continue;
+    const long pg = block_table[b * MP + (t >> ps_shift)];
+    if (pg < 0 || pg >= P) continue;
+    const long dst = (((pg * H + h) << ps_shift) + (t & ((1L << ps_shift) - 1))) * C + sub * 8;
+    *(u16x8*)(k_pool + dst) = *(const u16x8*)(k + row * C + sub * 8);
+    *(u16x8*)(v_pool + dst) = *(const u16x8*)(v + row * C + sub * 8);
+  }
 }

@@ -266,6 +266,134 @@ def attn_decode_slots(q, k_cache, v_cache, kv_lens_dev, kv_lens_host, slots_dev,
                       for b, s in enumerate(slots)], dim=0)
 
 
+# Paged decode (ops.PAGED_API): the caches are pools (P,H,PS,C) of P pages of
+# PS positions and position p of batch row b lives at row p % PS of page
+# table[b][p // PS] of a (B,MP) table. The ragged op on the cache gathered
+# through the table; what append and store write is scattered back, row by
+# row, so nothing else in the pool changes.
+def _host_table(t, B, k_pool, who):
+    """(table rows as lists, P, PS) after the binding's checks of the shapes."""
+    if k_pool.dim() != 4:
+        raise RuntimeError(f"{who}: the pools must be (P,H,PS,C)")
+    P, PS = k_pool.shape[0], k_pool.shape[2]
+    if not 16 <= PS <= 128 or PS & (PS - 1):
+        raise RuntimeError(f"{who}: the page size must be a power of two in "
+                           f"[16, 128], got {PS}")
+    if t.is_cuda or t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1 \
+            or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise RuntimeError(f"{who}: the host block table must be a CPU integer "
+                           f"tensor ({B}, MP)")
+    return t.to(torch.int64), P, PS
+
+
+def _check_table_dev(dev, host, who):
+    """What the binding asks of the device copy, wherever one is given."""
+    if dev is not None and dev.is_cuda and \
+            (dev.dtype != torch.int32 or dev.shape != host.shape):
+        raise RuntimeError(f"{who}: block_table_dev must be int32 of shape "
+                           f"{tuple(host.shape)}")
+
+
+def _cover(table, b, lo, hi, P, PS, written, who):
+    """The binding's check of the entries that cover positions [lo, hi) of row
+    b; ``written``: the set of pages that receive writes (None: a read)."""
+    for j in range(lo // PS, -(-hi // PS)):
+        pg = int(table[b, j])
+        if not 0 <= pg < P:
+            raise RuntimeError(f"{who}: block_table[{b}][{j}] = {pg} is outside "
+                               f"the pool of {P} pages")
+        if written is not None:
+            if pg in written:
+                raise RuntimeError(f"{who}: page {pg} receives writes twice")
+            written.add(pg)
+
+
+def _page_rows(table, b, lo, hi, PS):
+    """Index tensors (page, row in page) of positions [lo, hi) of row b."""
+    p = torch.arange(lo, hi)
+    return table[b, p // PS], p % PS
+
+
+def kv_append_paged(qkv, qw, kw, sin, cos, k_pool, v_pool, pos_dev, pos_host,
+                    table_dev, table_host, eps):
+    who = "kv_append_paged"
+    B, Tn = qkv.shape[:2]
+    pos = _host_lens(pos_host, B, who)
+    table, P, PS = _host_table(table_host, B, k_pool, who)
+    _check_table_dev(table_dev, table, who)
+    Tmax = table.shape[1] * PS
+    written = set()
+    for b, p in enumerate(pos):  # everything before the first write
+        if p < 0 or p + Tn > Tmax:
+            raise RuntimeError(f"kv_append: rows [{p}, {p + Tn}) do not fit a "
+                               f"cache of {Tmax} rows")
+        if sin.shape[0] < p + Tn or cos.shape[0] < p + Tn:
+            raise RuntimeError(f"kv_append: sin/cos tables have {sin.shape[0]} rows, "
+                               f"position {p + Tn - 1} needed")
+        _cover(table, b, p, p + Tn, P, PS, written, who)
+    H, C = qkv.shape[3], qkv.shape[4]
+    qs = []
+    for b, p in enumerate(pos):
+        # rows [p, p+Tn) of the gathered cache are all the append touches
+        kg = k_pool.new_empty(1, H, Tmax, C)
+        vg = v_pool.new_empty(1, H, Tmax, C)
+        qs.append(kv_append_ragged(qkv[b:b + 1], qw, kw, sin, cos, kg, vg, None,
+                                   torch.tensor([p]), eps))
+        pg, r = _page_rows(table, b, p, p + Tn, PS)
+        k_pool[pg, :, r] = kg[0, :, p:p + Tn].transpose(0, 1)
+        v_pool[pg, :, r] = vg[0, :, p:p + Tn].transpose(0, 1)
+    return torch.cat(qs, dim=0)
+
+
+def _gather_pages(pool, table, b, n, PS):
+    """Positions [0, ceil(n / PS) * PS) of row b as a cache (1,H,*,C)."""
+    pages = pool[table[b, :-(-n // PS)]]                  # (n_pages,H,PS,C)
+    H, C = pool.shape[1], pool.shape[3]
+    return pages.permute(1, 0, 2, 3).reshape(1, H, -1, C)
+
+
+def attn_decode_paged(q, k_pool, v_pool, kv_lens_dev, kv_lens_host, table_dev,
+                      table_host, num_splits):
+    who = "attn_decode_paged"
+    B, Tq = q.shape[0], q.shape[2]
+    lens = _host_lens(kv_lens_host, B, who)
+    table, P, PS = _host_table(table_host, B, k_pool, who)
+    _check_table_dev(table_dev, table, who)
+    Tmax = table.shape[1] * PS
+    for b, n in enumerate(lens):
+        if n > Tmax:
+            raise RuntimeError(f"decode_attention: kv_len {n} exceeds the cache ({Tmax})")
+        if not 1 <= Tq <= min(16, n):
+            raise RuntimeError("decode_attention: 1 <= Tq <= min(16, kv_len) required "
+                               f"(Tq {Tq}, kv_len {n})")
+        _cover(table, b, 0, n, P, PS, None, who)   # shared pages are legal to read
+    return torch.cat([attn_decode_ragged(q[b:b + 1], _gather_pages(k_pool, table, b, n, PS),
+                                         _gather_pages(v_pool, table, b, n, PS), None,
+                                         torch.tensor([n]), num_splits)
+                      for b, n in enumerate(lens)], dim=0)
+
+
+def kv_store_paged(k, v, k_pool, v_pool, lens_dev, lens_host, table_dev, table_host):
+    who = "kv_store_paged"
+    B, H, T, C = k.shape
+    lens = _host_lens(lens_host, B, who)
+    table, P, PS = _host_table(table_host, B, k_pool, who)
+    _check_table_dev(table_dev, table, who)
+    if v.shape != k.shape or k_pool.shape != v_pool.shape or \
+            (k_pool.shape[1], k_pool.shape[3]) != (H, C):
+        raise RuntimeError(f"{who}: k, v must be (B,H,T,C) and the pools (P,H,PS,C)")
+    written = set()
+    for b, n in enumerate(lens):
+        if not 0 <= n <= min(T, table.shape[1] * PS):
+            raise RuntimeError(f"{who}: length {n} exceeds the {T} rows given or "
+                               f"the table's {table.shape[1] * PS}")
+        _cover(table, b, 0, n, P, PS, written, who)
+    for b, n in enumerate(lens):
+        pg, r = _page_rows(table, b, 0, n, PS)
+        k_pool[pg, :, r] = k[b, :, :n].transpose(0, 1).to(k_pool.dtype)
+        v_pool[pg, :, r] = v[b, :, :n].transpose(0, 1).to(v_pool.dtype)
+
+
 # Seeded token sampling (ops.SAMPLING_API): top-k + Gumbel-max, the
 # definition of csrc/sampling.hip in fp32 on the logits' device. The Philox
 # words come from the host mirror, so one (seed, step) gives one stream on

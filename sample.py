@@ -6,7 +6,8 @@
 one prompt per line: more than one prompt decodes as one ragged batch
 (``generate_ragged``), one sample per prompt, ``--num_samples`` ignored; with
 ``--slots N`` they go through ``generate_continuous`` on N cache slots instead
-(continuous batching: there may be more prompts than slots).
+(continuous batching: there may be more prompts than slots), and with
+``--pages P [--page_size PS]`` on a paged cache of P pages shared by the slots.
 
 Loads config.json + the latest checkpoint from the rundir, rebuilds the
 model, and generates. Improvement over the reference (which re-runs a full
@@ -98,7 +99,14 @@ def main():
     p.add_argument("--slots", type=int, default=0,
                    help="several prompts: decode them by continuous batching on "
                         "this many cache slots (0: one ragged batch)")
+    p.add_argument("--pages", type=int, default=None,
+                   help="with --slots: a paged cache of this many pages shared by "
+                        "the slots (default: one whole cache per slot)")
+    p.add_argument("--page_size", type=int, default=16,
+                   help="with --pages: positions per page, a power of two in [16, 128]")
     args = p.parse_args()
+    if args.pages is not None and args.slots <= 0:
+        p.error("--pages needs --slots N")
 
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model, encode, decode, config = load_model_and_tokenizer(args.ckpt_dir,
@@ -117,7 +125,8 @@ def main():
         if args.slots > 0:
             outs = generate_continuous(model, prompts, args.max_new_tokens,
                                        temperature=args.temperature, top_k=args.top_k,
-                                       eos_id=args.eos_id, num_slots=args.slots, seed=seed)
+                                       eos_id=args.eos_id, num_slots=args.slots, seed=seed,
+                                       num_pages=args.pages, page_size=args.page_size)
         else:
             outs = generate_ragged(model, prompts, args.max_new_tokens,
                                    temperature=args.temperature, top_k=args.top_k,

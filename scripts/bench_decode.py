@@ -51,6 +51,16 @@
                     batches of 8 (each batch runs to its longest budget), the
                     two alternating in this process, each warmed up. Tokens/s =
                     tokens requested / wall time.
+                    With --pages: the same 32 requests on the unpaged
+                    DecodeScheduler with 8 slots against DecodeScheduler on a
+                    PagedKVCache of the same byte size (8 * block_size /
+                    page_size pages of --page_size positions) with 8, 16 and
+                    32 seats, the four alternating.
+  --which paged     attn_decode_paged and kv_append_paged with the pages in
+                    order and scrambled, page sizes 16, 64 and 128, against the
+                    slotted ops with the identity map on caches of the same
+                    byte size, all alternating x 3, at the --which slots
+                    shapes.
 """
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -286,6 +296,110 @@ def bench_slots(B, H, C, kv_len):
     del caches
 
 
+def bench_paged(B, H, C, kv_len, page_sizes=(16, 64, 128)):
+    """attn_decode_paged (pages in order, pages scrambled; every page size)
+    against attn_decode_slots with the identity map, all alternating over
+    rings of the same byte size; then the same for kv_append at Tn = 1."""
+    nbytes = 2 * B * H * kv_len * C * 2
+    ring = max(1, min(32, -(-RING_BYTES // nbytes)))
+    q = torch.randn(B, H, 1, C, device=DEV, dtype=BF)
+    lens_host = torch.full((B,), kv_len, dtype=torch.int64)
+    lens_dev = lens_host.to(device=DEV, dtype=torch.int32)
+    ident = torch.arange(B)
+    ident_dev = ident.to(device=DEV, dtype=torch.int32)
+    caches = [(torch.randn(B, H, kv_len, C, device=DEV, dtype=BF),
+               torch.randn(B, H, kv_len, C, device=DEV, dtype=BF))
+              for _ in range(ring)]
+    iters = 200 if nbytes < (64 << 20) else 50
+    paths = {"slots identity": [(lambda k=k, v=v: ops._C.attn_decode_slots(
+        q, k, v, lens_dev, lens_host, ident_dev, ident, 0)) for k, v in caches]}
+    qkv = torch.randn(B, 1, 3, H, C, device=DEV, dtype=BF)
+    qw = torch.ones(C, device=DEV)
+    sin, cos = (t.contiguous() for t in ref.rope_tables(C, kv_len, device=DEV))
+    pos_host = torch.full((B,), kv_len - 1, dtype=torch.int64)
+    pos_dev = pos_host.to(device=DEV, dtype=torch.int32)
+    kc, vc = caches[0]
+    appends = {"slots identity": [lambda: ops._C.kv_append_slots(
+        qkv, qw, qw, sin, cos, kc, vc, pos_dev, pos_host, ident_dev, ident, 1e-6)]}
+    for PS in page_sizes:
+        MP = kv_len // PS
+        P = B * MP
+        pools = [(torch.randn(P, H, PS, C, device=DEV, dtype=BF),
+                  torch.randn(P, H, PS, C, device=DEV, dtype=BF)) for _ in range(ring)]
+        order = torch.arange(P).view(B, MP)
+        mixed = torch.randperm(P, generator=torch.Generator().manual_seed(PS)).view(B, MP)
+        for tag, th in (("in order", order), ("scrambled", mixed)):
+            td = th.to(device=DEV, dtype=torch.int32)
+            paths[f"paged PS{PS} {tag}"] = [
+                (lambda k=k, v=v, td=td, th=th: ops._C.attn_decode_paged(
+                    q, k, v, lens_dev, lens_host, td, th, 0)) for k, v in pools]
+            kp, vp = pools[0]
+            appends[f"paged PS{PS} {tag}"] = [
+                lambda kp=kp, vp=vp, td=td, th=th: ops._C.kv_append_paged(
+                    qkv, qw, qw, sin, cos, kp, vp, pos_dev, pos_host, td, th, 1e-6)]
+    for what, group, n in (("attn_decode", paths, iters), ("kv_append  ", appends, 500)):
+        res = {name: [] for name in group}
+        for _ in range(3):                                # alternating
+            for name, fns in group.items():
+                res[name].append(time_ring(fns, n) * 1e6)
+        base = statistics.median(res["slots identity"])
+        for name, r in res.items():
+            print(f"{what} {name:22s} B{B} H{H} C{C} kv{kv_len}: "
+                  f"{statistics.median(r):9.1f} us (min {min(r):.1f} max {max(r):.1f})  "
+                  f"{statistics.median(r)/base:5.3f}x slots", flush=True)
+    del caches, paths, appends
+
+
+def bench_continuous_paged(reps, page_size, n_req=32, num_slots=8, seats=(8, 16, 32)):
+    from midgpt_amd.generate import DecodeScheduler
+    model, cfg = xl_model()
+    lens = [16, 48, 96, 160, 240, 320, 416, 512]
+    budgets = [16, 64, 128, 256]
+    g = torch.Generator().manual_seed(0)
+    reqs = [(torch.randint(0, cfg.vocab_size, (lens[i % 8],), generator=g).to(DEV),
+             budgets[i % 4]) for i in range(n_req)]
+    asked = sum(n for _, n in reqs)
+    num_pages = num_slots * cfg.block_size // page_size
+    print(f"continuous paged: openwebtext_xl, {n_req} requests, prompts cycling {lens}, "
+          f"budgets cycling {budgets} ({asked} tokens requested), greedy; unpaged with "
+          f"{num_slots} slots against {num_pages} pages of {page_size} (the same bytes) "
+          f"with {list(seats)} seats; time includes the prompts", flush=True)
+
+    def run(rs, n, **pages):
+        sched = DecodeScheduler(model, n, **pages)
+        hs = [sched.submit(p, m, temperature=0.0) for p, m in rs]
+        sched.run()
+        assert [h.tokens.numel() for h in hs] == [p.numel() + m for p, m in rs]
+        return [h.tokens for h in hs]
+
+    paths = {f"unpaged {num_slots} slots": lambda rs: run(rs, num_slots)}
+    for n in seats:
+        paths[f"paged PS{page_size} {n} seats"] = \
+            lambda rs, n=n: run(rs, n, num_pages=num_pages, page_size=page_size)
+    warm = [(p, 8) for p, _ in reqs[:2 * num_slots]]
+    for fn in paths.values():                             # warm up all
+        fn(warm)
+    res = {name: [] for name in paths}
+    texts = {}
+    for _ in range(reps):                                 # alternating
+        for name, fn in paths.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            texts[name] = fn(reqs)
+            torch.cuda.synchronize()
+            res[name].append(time.perf_counter() - t0)
+    base_name = f"unpaged {num_slots} slots"
+    base = statistics.median(res[base_name])
+    for name, ts in res.items():
+        tps = sorted(asked / t for t in ts)
+        same = sum(torch.equal(a, b) for a, b in zip(texts[name], texts[base_name]))
+        print(f"continuous {name:24s}: tokens/s median {statistics.median(tps):8.1f} "
+              f"min {tps[0]:8.1f} max {tps[-1]:8.1f}  (wall median "
+              f"{statistics.median(ts)*1e3:8.1f} ms) over {reps} runs, "
+              f"{base/statistics.median(ts):.2f}x unpaged, {same}/{n_req} texts equal "
+              "to unpaged", flush=True)
+
+
 def bench_continuous(reps, n_req=32, num_slots=8):
     from midgpt_amd.generate import DecodeScheduler, generate_ragged
     model, cfg = xl_model()
@@ -472,11 +586,14 @@ def run_count(n_new, sampled):
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--which", default="all", choices=["all", "kernels", "ragged", "e2e", "count", "sampling", "slots",
-                            "continuous"])
+                            "continuous", "paged"])
     p.add_argument("--sweep", action="store_true")
     p.add_argument("--reps", type=int, default=3)
     p.add_argument("--new", type=int, default=32)
     p.add_argument("--sampled", action="store_true")
+    p.add_argument("--pages", action="store_true",
+                   help="with --which continuous: the paged scheduler against the unpaged")
+    p.add_argument("--page_size", type=int, default=16)
     args = p.parse_args()
     if args.which in ("all", "kernels"):
         for B in (1, 8, 64):
@@ -507,7 +624,14 @@ if __name__ == "__main__":
             for kv in (128, 1024):
                 bench_slots(B, 16, 128, kv)
             bench_slots(B, 32, 128, 4096)
-    if args.which in ("all", "continuous"):
+    if args.which == "continuous" and args.pages:
+        bench_continuous_paged(max(3, args.reps), args.page_size)
+    elif args.which in ("all", "continuous"):
         bench_continuous(max(3, args.reps))
+    if args.which in ("all", "paged"):
+        for B in (8, 64):
+            for kv in (128, 1024):
+                bench_paged(B, 16, 128, kv)
+            bench_paged(B, 32, 128, 4096)
     if args.which == "count":
         run_count(args.new, args.sampled)

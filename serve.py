@@ -7,6 +7,7 @@ same way sample.py does, then serves batched KV-cache generation
 (midgpt_amd/generate.py) over HTTP.
 
     python serve.py --ckpt_dir runs/xl [--host 127.0.0.1 --port 8000] [--slots N]
+                    [--pages P [--page_size PS]]
 
     POST /generate {"prompt": "...", "max_new_tokens": 200,
                     "temperature": 0.8, "top_k": null, "num_samples": 1,
@@ -23,7 +24,10 @@ same way sample.py does, then serves batched KV-cache generation
          with --slots N > 0: the request joins the running batch of a
          DecodeScheduler with N cache slots (continuous batching), so
          concurrent requests share decode steps; returns {"sample": "..."}.
-         Limits as for /generate_batch. With --slots 0 (the default): 503
+         Limits as for /generate_batch. With --slots 0 (the default): 503.
+         With --pages P the scheduler's cache is paged: N seats share P pages
+         of --page_size positions (default 16) and a request holds only the
+         pages it can write; one that needs more than P pages is refused
     GET  /healthz
 
 Sampling is seeded (``ops.sample_tokens``): "seed" fixes the text of a
@@ -62,9 +66,11 @@ class SchedulerWorker:
     there is work and sleeps on a condition otherwise. ``generate`` may be
     called from any number of threads and blocks until its request is done."""
 
-    def __init__(self, model, num_slots: int):
+    def __init__(self, model, num_slots: int, num_pages: int | None = None,
+                 page_size: int = 16):
         from midgpt_amd.generate import DecodeScheduler
-        self.sched = DecodeScheduler(model, num_slots)
+        self.sched = DecodeScheduler(model, num_slots, num_pages=num_pages,
+                                     page_size=page_size)
         self.inbox = collections.deque()
         self.wake = threading.Condition()
         self.closed = None        # the reason, once the thread is to end
@@ -124,7 +130,8 @@ class SchedulerWorker:
         return job.handle.tokens
 
 
-def build_app(ckpt_dir: str, device: str | None = None, num_slots: int = 0):
+def build_app(ckpt_dir: str, device: str | None = None, num_slots: int = 0,
+              num_pages: int | None = None, page_size: int = 16):
     from fastapi import FastAPI
     from pydantic import BaseModel
 
@@ -156,7 +163,8 @@ def build_app(ckpt_dir: str, device: str | None = None, num_slots: int = 0):
         seed: int | None = None
         eos_id: int | None = None
 
-    worker = SchedulerWorker(model, num_slots) if num_slots > 0 else None
+    worker = SchedulerWorker(model, num_slots, num_pages, page_size) \
+        if num_slots > 0 else None
 
     @contextlib.asynccontextmanager
     async def lifespan(app):
@@ -221,10 +229,17 @@ def main():
     p.add_argument("--slots", type=int, default=0,
                    help="cache slots of the continuous-batching scheduler behind "
                         "/generate_one (0: off)")
+    p.add_argument("--pages", type=int, default=None,
+                   help="with --slots: page the scheduler's cache, this many pages "
+                        "shared by the slots (default: one whole cache per slot)")
+    p.add_argument("--page_size", type=int, default=16,
+                   help="with --pages: positions per page, a power of two in [16, 128]")
     args = p.parse_args()
+    if args.pages is not None and args.slots <= 0:
+        p.error("--pages needs --slots N")
     import uvicorn
-    uvicorn.run(build_app(args.ckpt_dir, num_slots=args.slots), host=args.host,
-                port=args.port)
+    uvicorn.run(build_app(args.ckpt_dir, num_slots=args.slots, num_pages=args.pages,
+                          page_size=args.page_size), host=args.host, port=args.port)
 
 
 if __name__ == "__main__":

@@ -9,6 +9,8 @@
 //   m   <- b1*m + (1-b1)*g ;  v <- b2*v + (1-b2)*g^2
 //   upd <- mhat/(sqrt(vhat)+eps) + (wd/lr_peak)*theta
 //   theta <- theta - lr_t * upd
+// omb1 = 1-b1, omb2 = 1-b2 and the bias corrections bc1, bc2 come from the
+// host, computed in double and rounded once.
 // The clip coefficient is computed ON DEVICE from the all-reduced squared
 // norm (sq_sum) so the step path never syncs to host.
 #include "common.h"
@@ -18,7 +20,8 @@ __global__ void adamw_kernel(float* __restrict__ master,
                              float* __restrict__ m, float* __restrict__ v,
                              u16* __restrict__ out_bf16, int write_bf16,
                              const float* __restrict__ sq_sum,
-                             float lr, float b1, float b2, float eps,
+                             float lr, float b1, float b2,
+                             float omb1, float omb2, float eps,
                              float wd, float grad_scale, float clip_norm,
                              float bc1, float bc2, long n) {
   const float gnorm = sqrtf(sq_sum[0]) * grad_scale + 1e-12f;
@@ -34,8 +37,8 @@ __global__ void adamw_kernel(float* __restrict__ master,
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float gg = g[j] * coef;
-      mm[j] = b1 * mm[j] + (1.f - b1) * gg;
-      vv[j] = b2 * vv[j] + (1.f - b2) * gg * gg;
+      mm[j] = b1 * mm[j] + omb1 * gg;
+      vv[j] = b2 * vv[j] + omb2 * gg * gg;
       float mhat = mm[j] * bc1;
       float vhat = vv[j] * bc2;
       float upd = mhat / (sqrtf(vhat) + eps) + wd * th[j];
@@ -51,8 +54,8 @@ __global__ void adamw_kernel(float* __restrict__ master,
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const long i = (n & ~3L) + threadIdx.x;
     float gg = grad[i] * coef;
-    m[i] = b1 * m[i] + (1.f - b1) * gg;
-    v[i] = b2 * v[i] + (1.f - b2) * gg * gg;
+    m[i] = b1 * m[i] + omb1 * gg;
+    v[i] = b2 * v[i] + omb2 * gg * gg;
     float upd = (m[i] * bc1) / (sqrtf(v[i] * bc2) + eps) + wd * master[i];
     master[i] -= lr * upd;
     if (write_bf16) out_bf16[i] = f2b(master[i]);

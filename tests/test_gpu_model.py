@@ -165,7 +165,11 @@ def _two_proc_gpu_worker(rank, init_file, out_q):
 def test_two_process_one_gpu_zero_engine(tmp_path):
     """2 ranks sharing cuda:0 over gloo: exercises the CUDA engine's
     overlap pipeline + collectives + ZeRO sharding end-to-end in a real
-    multi-process setting (RCCL needs 2 devices; gloo does not)."""
+    multi-process setting (RCCL needs 2 devices; gloo does not).
+
+    This is the loose end-to-end check on a real model. The exact one --
+    every element of the reduced gradient, the piece map and flat_w after
+    the all-gather -- is test_gpu_engine_exact.py::test_world2_one_gpu_exact."""
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.SimpleQueue()

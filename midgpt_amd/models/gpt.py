@@ -51,14 +51,26 @@ def _init_linear_(w: torch.Tensor, in_features: int, generator=None):
 
 
 class Linear(nn.Module):
-    """Bias-free linear, weight (out, in)."""
+    """Bias-free linear, weight (out, in).
+
+    ``weight_t`` is an optional (in, out) image of ``weight.t()`` that the
+    training engine binds and keeps current (ShardedAdamW, "dgrad image").
+    With one bound, a bf16 training forward on the GPU goes through
+    ``ops.linear_wt``, whose dgrad GEMM reads the image; everything else
+    (eval, generate, decode, the CPU, a model without an engine) is
+    ``F.linear``."""
 
     def __init__(self, in_features: int, out_features: int, generator=None):
         super().__init__()
         self.weight = nn.Parameter(torch.empty(out_features, in_features))
         _init_linear_(self.weight, in_features, generator)
+        self.weight_t = None  # plain attribute: not a parameter, not in state_dict
 
     def forward(self, x):
+        wt = self.weight_t
+        if (wt is not None and torch.is_grad_enabled() and x.is_cuda
+                and x.dtype == torch.bfloat16 and self.weight.dtype == torch.bfloat16):
+            return ops.linear_wt(x, self.weight, wt)
         return F.linear(x, self.weight.to(x.dtype))
 
 

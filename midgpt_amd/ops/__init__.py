@@ -38,6 +38,8 @@ SAMPLING_API = ("sample_tokens",)
 SLOT_API = ("kv_append_slots", "attn_decode_slots", "sample_tokens_rows")
 # Paged decode (block-table caches), under the same rule.
 PAGED_API = ("kv_append_paged", "attn_decode_paged", "kv_store_paged")
+# Batched transpose of matrices inside a flat buffer, under the same rule.
+TRANSPOSE_API = ("transpose_batched",)
 
 
 def _try_load_ext():
@@ -868,6 +870,73 @@ def fused_mlp(x, w1, w2):
     shp = x.shape
     y = _FusedMLP.apply(x.reshape(-1, shp[-1]).contiguous(), w1, w2)
     return y.reshape(*shp[:-1], w2.shape[0])
+
+
+# ----------------------------------------------------------------------------
+# Linear with a transposed weight image. The forward is F.linear, unchanged.
+# The backward reads dx from ``wt`` = w.t() stored (in, out): dx = dy wt^T is
+# then the forward's TN GEMM layout, which hipBLASLt runs 11-16 % faster on
+# gfx950 than the NN layout of dx = dy w at the model's shapes
+# (profiles/dgrad_wt.md). dW is the NT call autograd issues for F.linear.
+# ``wt`` is a cache the caller keeps equal to w.t(); it gets no gradient.
+# ----------------------------------------------------------------------------
+class _LinearWt(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, wt):
+        ctx.save_for_backward(x, wt)
+        return torch.nn.functional.linear(x, w)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wt = ctx.saved_tensors
+        dy2d = dy.reshape(-1, dy.shape[-1])
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = dy2d.mm(wt.t()).view(x.shape)
+        if ctx.needs_input_grad[1]:
+            dw = dy2d.t().mm(x.reshape(-1, x.shape[-1]))
+        return dx, dw, None
+
+
+def linear_wt(x, w, wt):
+    """x (..., in) @ w(out, in)^T with the dgrad read from wt (in, out), which
+    must hold w.t() (the training engine refreshes it after every write of
+    the weights). x, w and wt share one dtype."""
+    if wt.shape != (w.shape[1], w.shape[0]) or not (x.dtype == w.dtype == wt.dtype):
+        raise RuntimeError(f"linear_wt: w {tuple(w.shape)} {w.dtype} needs an image "
+                           f"{(w.shape[1], w.shape[0])} of its dtype and x's "
+                           f"({x.dtype}), got {tuple(wt.shape)} {wt.dtype}")
+    return _LinearWt.apply(x, w, wt)
+
+
+# ----------------------------------------------------------------------------
+# Batched transpose: every matrix of a table, from offsets of one flat buffer
+# to offsets of another, in one launch (csrc/transpose.hip; any dtype on
+# ref_backend, bf16 on the GPU).
+# ----------------------------------------------------------------------------
+TRANSPOSE_TILE = ref_backend.TRANSPOSE_TILE
+
+
+def transpose_table(entries, device=None):
+    """(table_dev, table_host) for ``transpose_batched`` from (src_off,
+    dst_off, rows, cols) per matrix: int64 (n, 5), the fifth column the count
+    of 64x64 tiles before the matrix."""
+    rows5, tiles = [], 0
+    for (so, do, r, c) in entries:
+        rows5.append([int(so), int(do), int(r), int(c), tiles])
+        tiles += -(-int(r) // TRANSPOSE_TILE) * -(-int(c) // TRANSPOSE_TILE)
+    host = torch.tensor(rows5, dtype=torch.int64).reshape(-1, 5)
+    return (host if device is None else host.to(device)), host
+
+
+def transpose_batched(src, dst, table_dev, table_host, max_blocks: int = 0):
+    """dst[dst_off : dst_off + rows*cols] viewed (cols, rows) becomes the
+    transpose of src[src_off : src_off + rows*cols] viewed (rows, cols), for
+    every row of the table (``transpose_table``). Nothing else of dst is
+    written. ``table_host`` is the truth and is validated; ``table_dev`` is
+    the copy the kernel reads, under the same contract as ``pos_dev``.
+    ``max_blocks`` caps the grid (0: sized for the device)."""
+    _backend(src).transpose_batched(src, dst, table_dev, table_host, int(max_blocks))
 
 
 # ----------------------------------------------------------------------------

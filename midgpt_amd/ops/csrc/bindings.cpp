@@ -692,6 +692,46 @@ torch::Tensor gelu_bwd(torch::Tensor dy, torch::Tensor x) {
 }
 
 // ---------------------------------------------------------------------------
+// Batched transpose (transpose.hip): every matrix of the table, one launch.
+// table_host (n,5) int64 on the CPU is the truth and is validated here: every
+// matrix inside src, every image inside dst, the tile prefix consistent.
+// table_dev is its GPU copy, which the kernel reads and the caller keeps
+// equal to it (not compared: that would be a sync). max_blocks caps the grid
+// (0: enough workgroups to fill the device, the rest by grid-stride).
+void transpose_batched(torch::Tensor src, torch::Tensor dst, torch::Tensor table_dev,
+                       torch::Tensor table_host, int64_t max_blocks) {
+  Call c("transpose_batched", src);
+  const int64_t ns = src.numel(), nd = dst.numel();
+  const u16* sp = c.bf16(src, "src", flat(ns));
+  u16* dp = c.bf16_out(dst, "dst", flat(nd));
+  TORCH_CHECK(sp + ns <= dp || dp + nd <= sp, c.who, ": src and dst overlap");
+  TORCH_CHECK(!table_host.is_cuda() && table_host.dim() == 2 && table_host.size(1) == TR_COLS &&
+              table_host.scalar_type() == torch::kLong && table_host.is_contiguous(),
+              c.who, ": the host table must be a contiguous CPU int64 tensor (n, 5)");
+  const int64_t n = table_host.size(0);
+  TORCH_CHECK(n <= INT_MAX, c.who, ": too many matrices");
+  const long* tp = c.i64(table_dev, "table_dev", {n, TR_COLS});
+  const int64_t* h = table_host.data_ptr<int64_t>();
+  int64_t tiles = 0;
+  for (int64_t m = 0; m < n; ++m, h += TR_COLS) {
+    const int64_t so = h[0], d_o = h[1], rows = h[2], cols = h[3];
+    TORCH_CHECK(rows >= 1 && cols >= 1 && rows <= ns && cols <= ns / rows,
+                c.who, ": matrix ", m, " is ", rows, " x ", cols, ", src holds ", ns);
+    const int64_t numel = rows * cols;
+    TORCH_CHECK(so >= 0 && so <= ns - numel, c.who, ": matrix ", m, " at ", so, " leaves src");
+    TORCH_CHECK(d_o >= 0 && numel <= nd && d_o <= nd - numel,
+                c.who, ": image ", m, " at ", d_o, " leaves dst");
+    TORCH_CHECK(h[4] == tiles, c.who, ": tile prefix of matrix ", m, " is ", h[4],
+                ", expected ", tiles);
+    tiles += ((rows + TR_TILE - 1) / TR_TILE) * ((cols + TR_TILE - 1) / TR_TILE);
+  }
+  TORCH_CHECK(max_blocks >= 0, c.who, ": max_blocks must be >= 0");
+  const int64_t cap = max_blocks > 0 ? max_blocks : 2048;  // 8 workgroups on each of 256 CUs
+  launch(transpose_batched_kernel, (unsigned)std::min(tiles, cap), 256, 0, sp, dp, tp, (int)n,
+         (long)tiles);
+}
+
+// ---------------------------------------------------------------------------
 // KV-cache decode (decode.hip). Caches are (B,H,Tmax,C) bf16, contiguous;
 // returns Tmax. pool: the caches are a pool of S >= B slots, (S,H,Tmax,C),
 // and *pool receives S.
@@ -1229,6 +1269,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("embedding_bwd", &embedding_bwd);
   mod.def("gelu_fwd", &gelu_fwd);
   mod.def("gelu_bwd", &gelu_bwd);
+  mod.def("transpose_batched", &transpose_batched, py::arg("src"), py::arg("dst"),
+          py::arg("table_dev"), py::arg("table_host"), py::arg("max_blocks") = 0);
   mod.def("lt_probe", &lt_probe);
   mod.def("matmul_dgelu", &matmul_dgelu);
   mod.def("probe_mfma", &probe_mfma);

@@ -9,5 +9,6 @@
 #include "embedding.hip"
 #include "gelu.hip"
 #include "sampling.hip"
+#include "transpose.hip"
 #include "probe.hip"
 #include "bindings.cpp"

@@ -1,6 +1,7 @@
 """The extension's interface in fp32 torch: one plain function (no autograd)
 per entry point in ``ops.BACKEND_API``, ``ops.RAGGED_API``,
-``ops.SAMPLING_API`` and ``ops.SLOT_API``, taking the same positional arguments
+``ops.SAMPLING_API``, ``ops.SLOT_API``, ``ops.PAGED_API`` and
+``ops.TRANSPOSE_API``, taking the same positional arguments
 as the ``_C`` binding of that name and returning as many results with the
 same shapes and dtypes. ``ops._backend`` hands out this module wherever the
 HIP extension does not run: on the CPU and under ``MIDGPT_FORCE_REF=1``.
@@ -521,3 +522,33 @@ def adamw_step(master, grad, m, v, out_bf16, write_bf16, sq_sum, lr, beta1, beta
     master.add_(update, alpha=-lr)
     if write_bf16:
         out_bf16.copy_(master.to(torch.bfloat16))
+
+
+# Batched transpose (ops.TRANSPOSE_API): matrix m of the table, rows x cols
+# at src[src_off:], lands transposed at dst[dst_off:]. The host table (n, 5)
+# int64 {src_off, dst_off, rows, cols, tile prefix} is the truth and is
+# validated as the binding validates it; any dtype goes.
+TRANSPOSE_TILE = 64
+
+
+def transpose_batched(src, dst, table_dev, table_host, max_blocks=0):
+    who = "transpose_batched"
+    if src.dim() != 1 or dst.dim() != 1 or src.dtype != dst.dtype:
+        raise RuntimeError(f"{who}: src and dst must be flat buffers of one dtype")
+    t = table_host
+    if t.is_cuda or t.dim() != 2 or t.shape[1] != 5 or t.dtype != torch.int64:
+        raise RuntimeError(f"{who}: the host table must be a CPU int64 tensor (n, 5)")
+    if tuple(table_dev.shape) != tuple(t.shape):
+        raise RuntimeError(f"{who}: the device table must be {tuple(t.shape)}")
+    tiles = 0
+    for m, (so, do, rows, cols, prefix) in enumerate(t.tolist()):
+        if rows < 1 or cols < 1 or so < 0 or so + rows * cols > src.numel():
+            raise RuntimeError(f"{who}: matrix {m} ({rows} x {cols} at {so}) leaves src")
+        if do < 0 or do + rows * cols > dst.numel():
+            raise RuntimeError(f"{who}: image {m} at {do} leaves dst")
+        if prefix != tiles:
+            raise RuntimeError(f"{who}: tile prefix of matrix {m} is {prefix}, "
+                               f"expected {tiles}")
+        tiles += -(-rows // TRANSPOSE_TILE) * -(-cols // TRANSPOSE_TILE)
+        dst[do:do + rows * cols].view(cols, rows).copy_(
+            src[so:so + rows * cols].view(rows, cols).t())

@@ -33,6 +33,21 @@ launched in strictly DESCENDING index order (backward produces grads in
 reverse registration order), which also guarantees an identical collective
 launch order on every rank.
 
+Dgrad image: beside ``flat_w`` the engine keeps ONE flat bf16 buffer
+``flat_wt`` holding ``weight.t()`` of every ``Linear`` of the model, and
+binds a view of it to each module (``Linear.weight_t``), whose backward then
+reads dx = dy Wt^T in the forward's GEMM layout (``ops.linear_wt``). One
+batched-transpose launch refreshes every image after each writer of
+``flat_w``: the end of ``__init__``, ``step()`` (after ``adamw_step``; under
+ZeRO after the all-gather, on the compute stream, which the synchronous
+collective has made wait for the gathered weights) and ``refresh_weights()``
+(hence ``load_state_full``). Nothing else writes the weights in training,
+and they do not change between the microbatches of a step or between a
+forward and its backward; code that writes ``flat_w`` or a parameter by hand
+calls ``refresh_dgrad_images()`` afterwards. Only on the GPU, in bf16, with
+the extension loaded and a model that has ``Linear`` modules;
+``MIDGPT_DGRAD_WT=0`` turns it off (no buffer, no launch).
+
 Numerics parity with the reference step (src/train.py:79-97):
 bf16 grads reduced across ranks, accumulated in fp32 per microbatch;
 clip_by_global_norm(1.0) -> Adam(b1=.9, b2=cfg) -> + (wd/lr_peak)*theta
@@ -173,6 +188,41 @@ class ShardedAdamW:
         if self._hooks_on:
             for i, p in enumerate(self.params):
                 p.register_post_accumulate_grad_hook(self._make_hook(i))
+        self._init_dgrad_images()
+
+    # ------------------------------------------------------------------
+    # dgrad image (see the module docstring)
+    # ------------------------------------------------------------------
+    def _init_dgrad_images(self):
+        from midgpt_amd.models.gpt import Linear
+        self.flat_wt = None
+        if (self.device.type != "cuda" or self.compute_dtype != torch.bfloat16
+                or not ops.have_ext()
+                or os.environ.get("MIDGPT_DGRAD_WT", "1") == "0"):
+            return
+        offset = {id(p): (o, shape) for p, (_, shape, o, _) in zip(self.params, self.meta)}
+        linears = [m for m in self.model.modules()
+                   if isinstance(m, Linear) and id(m.weight) in offset]
+        if not linears:
+            return
+        entries, off = [], 0
+        for m in linears:
+            o, (rows, cols) = offset[id(m.weight)]
+            entries.append((o, off, rows, cols))
+            # every image starts 16-byte aligned, whatever the one before holds
+            off += -(-rows * cols // 8) * 8
+        self.flat_wt = torch.empty(off, dtype=self.compute_dtype, device=self.device)
+        self._wt_table_dev, self._wt_table = ops.transpose_table(entries, self.device)
+        for m, (_, do, rows, cols) in zip(linears, entries):
+            m.weight_t = self.flat_wt[do:do + rows * cols].view(cols, rows)
+        self.refresh_dgrad_images()
+
+    def refresh_dgrad_images(self):
+        """Recompute every bound ``weight.t()`` image from ``flat_w``: one
+        launch on the current stream; nothing without images."""
+        if self.flat_wt is not None:
+            ops.transpose_batched(self.flat_w, self.flat_wt, self._wt_table_dev,
+                                  self._wt_table)
 
     # ------------------------------------------------------------------
     def _take_shard(self, full: torch.Tensor) -> torch.Tensor:
@@ -340,6 +390,7 @@ class ShardedAdamW:
             out_view.copy_(self.master.to(self.compute_dtype))
         if self.zero:
             self._allgather_weights()
+        self.refresh_dgrad_images()
         self.g32.zero_()
         return sq
 
@@ -391,6 +442,7 @@ class ShardedAdamW:
             self._allgather_weights()
         else:
             self.flat_w.copy_(self.master.to(self.compute_dtype))
+        self.refresh_dgrad_images()
 
     def named_param_manifest(self) -> list[dict]:
         """Ordered named-parameter manifest (the flat-leaves contract of the

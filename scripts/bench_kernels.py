@@ -127,11 +127,88 @@ def bench_gemm():
         print(f"gemm {tag} {M}x{K}x{N}: {t*1e3:8.3f} ms  {fl/t/1e12:7.1f} TF/s")
 
 
+def bench_dgrad(M=65536, rounds=5, iters=8):
+    """dgrad dx = dy W as torch issues it today (NN, W stored (out, in))
+    against the same product from a transposed image Wt (in, out), which is
+    the forward's TN layout. The two run interleaved, round by round, in this
+    one process; the figure per variant is the median round. Weighted by
+    launches per microstep it predicts the step's saving."""
+    shapes = [("c_attn", 2048, 6144, 24), ("attn_proj", 2048, 2048, 24),
+              ("c_fc", 2048, 8192, 24), ("mlp_proj", 8192, 2048, 24),
+              ("lm_head", 2048, 50304, 1)]
+
+    def window(fn):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    total_nn = total_tn = 0.0
+    print(f"dgrad M={M}: NN (dy @ W) vs TN (dy @ Wt.t()), ms per call, "
+          f"median of {rounds} interleaved rounds of {iters}")
+    print("| shape | in | out | NN ms | NN TF/s | TN ms | TN TF/s | TN/NN | "
+          "launches | saved ms/microstep |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for tag, n_in, n_out, launches in shapes:
+        dy = torch.randn(M, n_out, device=DEV, dtype=torch.bfloat16)
+        w = (torch.randn(n_out, n_in, device=DEV) / n_in ** 0.5).to(torch.bfloat16)
+        wt = w.t().contiguous()
+        nn_fn = lambda: torch.mm(dy, w)
+        tn_fn = lambda: torch.mm(dy, wt.t())
+        for _ in range(3):
+            nn_fn()
+            tn_fn()
+        torch.cuda.synchronize()
+        t_nn, t_tn = [], []
+        for _ in range(rounds):
+            t_nn.append(window(nn_fn))
+            t_tn.append(window(tn_fn))
+        a = sorted(t_nn)[rounds // 2]
+        b = sorted(t_tn)[rounds // 2]
+        fl = 2.0 * M * n_in * n_out
+        saved = (a - b) * launches
+        total_nn += a * launches
+        total_tn += b * launches
+        print(f"| {tag} | {n_in} | {n_out} | {a:.3f} | {fl/a/1e9:.0f} | {b:.3f} | "
+              f"{fl/b/1e9:.0f} | {b/a:.3f} | {launches} | {saved:+.2f} |")
+        del dy, w, wt
+    print(f"weighted per microstep: NN {total_nn:.2f} ms, TN {total_tn:.2f} ms, "
+          f"saved {total_nn - total_tn:+.2f} ms")
+
+
+def bench_transpose(D=2048, L=24, V=50304):
+    """The engine's one launch at openwebtext_xl: every Linear weight of the
+    model transposed from a flat buffer into the image buffer, beside a torch
+    copy_ of the same byte count (the yardstick: read + write once)."""
+    shapes = [(3 * D, D), (D, D), (4 * D, D), (D, 4 * D)] * L + [(V, D)]
+    entries, off = [], 0
+    for r, c in shapes:
+        entries.append((off, off, r, c))
+        off += r * c
+    src = torch.randn(off, device=DEV, dtype=torch.bfloat16)
+    dst = torch.empty_like(src)
+    tdev, thost = ops.transpose_table(entries, DEV)
+    t = timeit(lambda: ops.transpose_batched(src, dst, tdev, thost), iters=10, warmup=3)
+    tc = timeit(lambda: dst.copy_(src), iters=10, warmup=3)
+    gb = 2 * off * 2 / 1e9
+    print(f"transpose_batched {len(shapes)} matrices, {off/1e9:.3f}e9 elements: "
+          f"{t*1e3:8.3f} ms  {gb/t/1e3:6.2f} TB/s   | copy_ {tc*1e3:8.3f} ms  "
+          f"{gb/tc/1e3:6.2f} TB/s   | ratio {t/tc:.2f}")
+
+
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--which", default="all")
     args = p.parse_args()
     w = args.which
+    if w == "dgrad":  # a decision measurement of its own, not part of "all"
+        bench_dgrad()
+    if w in ("all", "transpose"):
+        bench_transpose()
     if w in ("all", "attn"):
         bench_attn()
         bench_attn(B=32, H=12, T=1024, C=64)

@@ -89,7 +89,11 @@ struct RmStage {
 };
 // Row-pair loader -> transposed image (u16x2 pair writes), and optionally
 // also the row-major image (both from ONE set of global loads).
-template <int C, int NT>
+// ACCK (the backward kernels): the transposed image has its 32 rows at
+// acc_k_pos (mfma.h) inside each image row, for a reader whose other operand
+// is a dlayout_pack'ed accumulator, and both code paths below are the ones
+// that keep a tile loop's staging in registers from load to ds_write.
+template <int C, int NT, bool ACCK = false>
 struct TrStage {
   static constexpr int NP = (32 * C + NT * 16 - 1) / (NT * 16);
   u16x8 a[NP], b[NP];  // rows 2p and 2p+1 at an 8-col span
@@ -109,17 +113,51 @@ struct TrStage {
       // issue time, not carried through the tile loop as a pointer of its own.
       int ldb = 2 * ld;
       asm volatile("" : "+s"(ldb));
+      if constexpr (ACCK) {
+        // Wave-uniform base plus a 32-bit lane offset, opaque so that the
+        // loop keeps no 64-bit per-lane pointer alive from tile to tile.
+        unsigned off = boff;
+        asm volatile("" : "+v"(off));
+        a[i] = *(const u16x8*)((const char*)gi + off);
+        b[i] = *(const u16x8*)((const char*)gi + ldb + off);
+        continue;
+      }
       a[i] = *(const u16x8*)pa;
       b[i] = *(const u16x8*)(pa + ldb);
     }
   }
+  // A row pair (2p, 2p+1) stays a pair under acc_k_pos.
   DEVINL void write_tr(u16* lds) const {
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int idx = threadIdx.x * 16 + i * NT * 16;
       if (idx >= 32 * C) continue;
-      const int row = 2 * (idx / (2 * C));
+      const int row0 = 2 * (idx / (2 * C));
+      const int row = ACCK ? acc_k_pos(row0) : row0;
       const int col = (idx / 2) % C;
+      if constexpr (ACCK) {
+        // The pairs are cut out of the loaded dwords with integer ops.
+        // Element-wise u16 extraction (below) makes the compiler keep a and
+        // b in a stack slot: every tile's loads are then waited for and
+        // stored to scratch where they are issued, and the prefetch hides
+        // nothing.
+        const u32x4 aw = __builtin_bit_cast(u32x4, a[i]);
+        const u32x4 bw = __builtin_bit_cast(u32x4, b[i]);
+        // col is a multiple of 8, so swz_tr(col + j, x) is
+        // x ^ 32*((col>>3)&1) ^ 16*(j>>2): two bases per thread and the
+        // rest in the store's offset field, not eight address registers.
+        const int x = (row * 2) ^ (((col >> 3) & 1) << 5);
+        char* const p0 = (char*)lds + col * 64 + x;
+        char* const p1 = (char*)lds + col * 64 + (x ^ 16);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {  // LDS row = col + j
+          const unsigned pv = (j & 1)
+              ? (aw[j >> 1] >> 16) | (bw[j >> 1] & 0xffff0000u)
+              : (aw[j >> 1] & 0xffffu) | (bw[j >> 1] << 16);
+          *(unsigned*)((j < 4 ? p0 : p1) + j * 64) = pv;
+        }
+        continue;
+      }
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int r = col + j;  // LDS row = c
@@ -145,9 +183,9 @@ template <int C, int NT>
 DEVINL void stage_rm(const u16* __restrict__ g, u16* lds, int ld = C) {
   RmStage<C, NT> st; st.load(g, ld); st.write(lds);
 }
-template <int C, int NT>
+template <int C, int NT, bool ACCK = false>
 DEVINL void stage_tr(const u16* __restrict__ g, u16* lds, int ld = C) {
-  TrStage<C, NT> st; st.load(g, ld); st.write_tr(lds);
+  TrStage<C, NT, ACCK> st; st.load(g, ld); st.write_tr(lds);
 }
 
 // Read one A/B fragment (bf16x8) from a swizzled row-major [R][C] tile:
@@ -161,30 +199,6 @@ DEVINL bf16x8_t read_tr_frag(const u16* lds, int row, int kbyte) {
 }
 
 DEVINL float shfl32(float v, int src) { return __shfl(v, src, 32); }
-
-// dlayout_to_afrag (mfma.h) with a dropout keep mask: bit i of m8 clear
-// zeroes s[i]. The mask is applied to the packed bf16 pairs, so no second
-// fp32 copy of the 8 values is ever live.
-DEVINL bf16x8_t dlayout_to_afrag_keep(const float* s /*8 vals*/, uint32_t m8) {
-  unsigned x[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const unsigned mk = (((m8 >> (2 * i)) & 1u) ? 0x0000ffffu : 0u) |
-                        (((m8 >> (2 * i + 1)) & 1u) ? 0xffff0000u : 0u);
-    x[i] = pack_bf16(s[2 * i], s[2 * i + 1]) & mk;
-  }
-  {
-    auto r = __builtin_amdgcn_permlane32_swap(x[0], x[2], false, false);
-    x[0] = r[0]; x[2] = r[1];
-  }
-  {
-    auto r = __builtin_amdgcn_permlane32_swap(x[1], x[3], false, false);
-    x[1] = r[0]; x[3] = r[1];
-  }
-  union { unsigned u[4]; bf16x8_t v; } out;
-  out.u[0] = x[0]; out.u[1] = x[1]; out.u[2] = x[2]; out.u[3] = x[3];
-  return out.v;
-}
 
 // ===========================================================================
 // Forward. SPW strips per wave: with SPW=2 each wave owns MIRRORED strips
@@ -579,7 +593,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
 }
 
 // ===========================================================================
-// delta = rowsum(dO * O) — one wave per row (prologue of backward)
+// delta = rowsum(dO * O) — 64/(C/8) rows per wave (prologue of backward)
 // Unchanged under dropout: with O_i = sum_j P_ij Z_ij V_j (Z = keep/(1-p)),
 // dO_i.O_i = sum_j P_ij Z_ij (dO_i.V_j) = sum_j P_ij dP_ij, dP = (dO V^T)oZ.
 // ===========================================================================
@@ -589,14 +603,22 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
 // on the way, for the dkv and dq kernels to stage from (their per-head tiles
 // are then contiguous; read in place from (B,T,H,C), whose rows of one head
 // lie H*C elements apart, both kernels measured 8-12% slower).
+// A row is C/8 lanes of 16 bytes, so a wave takes 64/(C/8) consecutive rows
+// at once and sums each within its own lane group.
+template <int C>
 __global__ void attn_delta_kernel(const u16* __restrict__ dO,
                                   const u16* __restrict__ O,
-                                  float* __restrict__ delta, long N, int C,
+                                  float* __restrict__ delta, long N,
                                   int H, int T, AttnStrides sdo, AttnStrides so,
                                   u16* __restrict__ do_copy, int bth_order) {
+  constexpr int LPR = C / 8;      // lanes per row
+  constexpr int RPW = WAVE / LPR;  // rows per wave
+  static_assert(LPR * 8 == C && RPW * LPR == WAVE, "C/8 must divide the wave");
   const int lane = lane_id();
-  const long row0 = (long)blockIdx.x * (blockDim.x / WAVE) + wave_id();
-  const long rstep = (long)gridDim.x * (blockDim.x / WAVE);
+  const int i = (lane % LPR) * 8;
+  const long row0 =
+      ((long)blockIdx.x * (blockDim.x / WAVE) + wave_id()) * RPW + lane / LPR;
+  const long rstep = (long)gridDim.x * (blockDim.x / WAVE) * RPW;
   for (long row = row0; row < N; row += rstep) {
     // N < 2^31 (checked by the launcher): 32-bit divisions
     const unsigned urow = (unsigned)row;
@@ -612,15 +634,14 @@ __global__ void attn_delta_kernel(const u16* __restrict__ dO,
     const u16* dor = dO + bh_base(sdo, bh, H) + t * sdo.r;
     const u16* orow = O + bh_base(so, bh, H) + t * so.r;
     float acc = 0.f;
-    for (int i = lane * 8; i < C; i += WAVE * 8) {
-      u16x8 a = *(const u16x8*)(dor + i);
-      u16x8 b = *(const u16x8*)(orow + i);
-      if (do_copy) *(u16x8*)(do_copy + (bh * T + t) * C + i) = a;
+    const u16x8 a = *(const u16x8*)(dor + i);
+    const u16x8 b = *(const u16x8*)(orow + i);
+    if (do_copy) *(u16x8*)(do_copy + (bh * T + t) * C + i) = a;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) acc += b2f(a[j]) * b2f(b[j]);
-    }
-    acc = group_sum<WAVE>(acc);
-    if (lane == 0) delta[bh * T + t] = acc;
+    for (int j = 0; j < 8; ++j) acc += b2f(a[j]) * b2f(b[j]);
+    // a row's lanes leave the loop together, so its group is whole here
+    acc = group_sum<LPR>(acc);
+    if (lane % LPR == 0) delta[bh * T + t] = acc;
   }
 }
 
@@ -636,6 +657,17 @@ __global__ void attn_delta_kernel(const u16* __restrict__ dO,
 // dS = P o (dP - delta) * scale. Registers 4g..4g+3 are four consecutive q
 // (4-aligned) at this lane's k: one Philox call per register group. The
 // 1/(1-p) of dV is applied once, in the epilogue.
+// Whether the dkv kernel keeps its V fragments in LDS (NW*32*C bf16 behind
+// the staging buffers). Not at C=128 with 4 waves: two such workgroups share
+// a CU, and 96.5 KB each would leave room for one. There V is re-read from
+// global (L2) in every tile.
+template <int C, int NW>
+constexpr bool attn_dkv_vf_lds = !(C == 128 && NW == 4);
+// How many of a lane's C/16 K fragments sit in LDS behind them (the DROP
+// kernel at C=128 keeps none resident and uses none of it).
+template <int C, int NW>
+constexpr int attn_dkv_kf_lds = C == 128 ? 3 : 0;
+
 template <int C, int NW, bool DROP = false>
 __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
     const u16* __restrict__ dO, const u16* __restrict__ q,
@@ -660,6 +692,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
   u16* base = (u16*)smem;                       // [2][TILE]
   float* ldsLse = (float*)(base + 2 * TILE);    // [2][32]
   float* ldsDelta = ldsLse + 64;                // [2][32]
+  // V fragments of this wave's 32 keys, constant over the q loop: each lane
+  // parks its own NCH fragments here once and reads back only those, so no
+  // barrier guards them and a 16-byte read per lane is conflict-free.
+  constexpr bool VF_LDS = attn_dkv_vf_lds<C, NW>;
+  bf16x8_t* ldsVf = (bf16x8_t*)(ldsDelta + 64) + w * (NCH * 64) + lane;
 
   const u16* qg = q + (bh * T) * C;
   const u16* kg = k + (bh * T) * C;
@@ -667,20 +704,36 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
   const u16* dog = dO + bh_base(sdo, bh, H);
   const u16* krow = kg + (long)myk * C;
   const u16* vrow = vg + (long)myk * sv.r;
+  if constexpr (VF_LDS) {
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch)
+      ldsVf[ch * 64] = *(const bf16x8_t*)(vrow + 16 * ch + 8 * (lane >> 5));
+  }
 
   // K row fragments resident in registers (the L2 re-read variant was
   // measured -20% on dkv C=128 in a full-step profile despite removing
   // the 2-VGPR spill — the per-tile global loads add latency the spill
   // never cost).
   // Under DROP at C=128 the keep mask and its select/scale code do not
-  // fit beside 32 VGPRs of resident K (the DROP=false kernel already sits
-  // at the 256 cap with 2 spills), so that variant re-reads K too.
+  // fit beside 32 VGPRs of resident K (the DROP=false kernel sits at the
+  // 256 cap), so that variant re-reads K too.
   constexpr bool KF_RES = !(DROP && C == 128);
-  bf16x8_t kf[KF_RES ? NCH : 1];
+  // At C=128 the last NKL of them are parked in LDS behind V in the same
+  // way: with the next tile's Q and dO held in registers across the compute
+  // phase, all NCH beside the 128 accumulators spill, and a scratch reload
+  // in the loop waits for the prefetch with it.
+  constexpr int NKL = KF_RES ? attn_dkv_kf_lds<C, NW> : 0;
+  constexpr int NKR = KF_RES ? NCH - NKL : 0;
+  bf16x8_t kf[NKR ? NKR : 1];
+  bf16x8_t* ldsKf = (bf16x8_t*)(ldsDelta + 64) + (VF_LDS ? NW * (NCH * 64) : 0) +
+                    w * (NKL * 64) + lane;
   if (KF_RES) {
 #pragma unroll
-    for (int ch = 0; ch < NCH; ++ch)
-      kf[ch] = *(const bf16x8_t*)(krow + 16 * ch + 8 * (lane >> 5));
+    for (int ch = 0; ch < NCH; ++ch) {
+      const bf16x8_t f = *(const bf16x8_t*)(krow + 16 * ch + 8 * (lane >> 5));
+      if (ch < NKR) kf[ch < NKR ? ch : 0] = f;
+      else ldsKf[(ch - NKR) * 64] = f;
+    }
   }
 
   f32x16 dvacc[NCB], dkacc[NCB];
@@ -694,9 +747,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
     const long qbase = (long)qt * 32;
     u16* bq = base + buf * TILE;
     stage_rm<C, NW * 64>(qg + qbase * C, bq);
-    stage_tr<C, NW * 64>(qg + qbase * C, bq + 32 * C);
+    stage_tr<C, NW * 64, true>(qg + qbase * C, bq + 32 * C);
     stage_rm<C, NW * 64>(dog + qbase * sdo.r, bq + 2 * 32 * C, sdo.r);
-    stage_tr<C, NW * 64>(dog + qbase * sdo.r, bq + 3 * 32 * C, sdo.r);
+    stage_tr<C, NW * 64, true>(dog + qbase * sdo.r, bq + 3 * 32 * C, sdo.r);
     if (threadIdx.x < 32) {
       ldsLse[buf * 32 + threadIdx.x] = lse[bh * T + qbase + threadIdx.x];
       ldsDelta[buf * 32 + threadIdx.x] = delta[bh * T + qbase + threadIdx.x];
@@ -705,7 +758,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
 
   stage_set(qt0, 0);
   __syncthreads();
-  TrStage<C, NW * 64> qst, dost;  // ONE load feeds both rm and tr images
+  // Every prologue load has landed: said outright, so that the vmcnt waits
+  // inside the loop count its own prefetch alone and none of them stands
+  // before the compute phase on account of a load from up here.
+  __builtin_amdgcn_s_waitcnt(0);
+  TrStage<C, NW * 64, true> qst, dost;  // ONE load feeds both rm and tr images
   float lse_r = 0.f, del_r = 0.f;
   for (int qt = qt0; qt < nqt; ++qt) {
     const int buf = (qt - qt0) & 1;
@@ -715,8 +772,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
       qst.load(qg + nb * C);
       dost.load(dog + nb * sdo.r, sdo.r);
       if (threadIdx.x < 32) {
-        lse_r = lse[bh * T + nb + threadIdx.x];
-        del_r = delta[bh * T + nb + threadIdx.x];
+        unsigned off = 4u * threadIdx.x;  // opaque, as in TrStage::load
+        asm volatile("" : "+v"(off));
+        lse_r = *(const float*)((const char*)(lse + bh * T + nb) + off);
+        del_r = *(const float*)((const char*)(delta + bh * T + nb) + off);
       }
     }
     const int qbase = qt * 32;
@@ -739,31 +798,35 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
                                   (uint32_t)myk, drop_thr) << (4 * g);
         __builtin_amdgcn_sched_barrier(0);
       }
+      // Registers 4g..4g+3 are q rows 8g + 4h .. +3 (h = lane>>5): the
+      // tile's LSE and delta come as four 16-byte reads each.
       // S = Q x K^T (D rows = q regs, cols = k lanes)
       f32x16 s = (f32x16)(0.f);
 #pragma unroll
       for (int ch = 0; ch < NCH; ++ch) {
         bf16x8_t a = read_rm_frag<C>(ldsQ, lane & 31, 16 * ch * 2 + 16 * (lane >> 5));
-        bf16x8_t kfr = KF_RES ? kf[ch]
-            : *(const bf16x8_t*)(krow + 16 * ch + 8 * (lane >> 5));
+        bf16x8_t kfr;
+        if constexpr (!KF_RES) kfr = *(const bf16x8_t*)(krow + 16 * ch + 8 * (lane >> 5));
+        else if (ch < NKR) kfr = kf[ch < NKR ? ch : 0];
+        else kfr = ldsKf[(ch - NKR) * 64];
         s = mfma_32x32x16_bf16(a, kfr, s);
       }
       float p[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int qrow = qbase + mfma_d_row(lane, r);
-        p[r] = (myk > qrow) ? 0.f
-             : __expf(s[r] * scale - lseb[mfma_d_row(lane, r)]);
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 l4 = *(const f32x4*)(lseb + 8 * g + 4 * (lane >> 5));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int r = 4 * g + i;
+          const int qrow = qbase + mfma_d_row(lane, r);
+          p[r] = (myk > qrow) ? 0.f : __expf(s[r] * scale - l4[i]);
+        }
       }
-      // dV += P^T x dO
-      bf16x8_t pf0, pf1;
-      if constexpr (DROP) {
-        pf0 = dlayout_to_afrag_keep(p, keep);
-        pf1 = dlayout_to_afrag_keep(p + 8, keep >> 8);
-      } else {
-        pf0 = dlayout_to_afrag(p);
-        pf1 = dlayout_to_afrag(p + 8);
-      }
+      // dV += P^T x dO. P^T x B sums over P's register (q) index: packed
+      // pairwise P is the A operand as it stands, against a dOt image whose
+      // q positions follow acc_k_pos. The same holds for dS and Qt below.
+      const bf16x8_t pf0 = dlayout_pack(p, DROP ? keep : 0xffu);
+      const bf16x8_t pf1 = dlayout_pack(p + 8, DROP ? keep >> 8 : 0xffu);
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
         bf16x8_t b0 = read_tr_frag(ldsDOt, 32 * cb + (lane & 31), 16 * (lane >> 5));
@@ -771,24 +834,32 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
         dvacc[cb] = mfma_32x32x16_bf16(pf0, b0, dvacc[cb]);
         dvacc[cb] = mfma_32x32x16_bf16(pf1, b1, dvacc[cb]);
       }
-      // dP = dO x V^T; V frags from global (L2-resident)
+      // dP = dO x V^T
       f32x16 dp = (f32x16)(0.f);
 #pragma unroll
       for (int ch = 0; ch < NCH; ++ch) {
         bf16x8_t a = read_rm_frag<C>(ldsDO, lane & 31, 16 * ch * 2 + 16 * (lane >> 5));
-        bf16x8_t vf = *(const bf16x8_t*)(vrow + 16 * ch + 8 * (lane >> 5));
+        bf16x8_t vf;
+        if constexpr (VF_LDS) vf = ldsVf[ch * 64];
+        else vf = *(const bf16x8_t*)(vrow + 16 * ch + 8 * (lane >> 5));
         dp = mfma_32x32x16_bf16(a, vf, dp);
       }
-      // dS = P * (dP - delta[q]) * scale; dK += dS^T x Q
+      // dS = P * (dP - delta[q]) * scale
       float ds[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float dpr = dp[r];
-        if constexpr (DROP) dpr = ((keep >> r) & 1u) ? dpr * inv_keep : 0.f;
-        ds[r] = p[r] * (dpr - deltab[mfma_d_row(lane, r)]) * scale;
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 d4 = *(const f32x4*)(deltab + 8 * g + 4 * (lane >> 5));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int r = 4 * g + i;
+          float dpr = dp[r];
+          if constexpr (DROP) dpr = ((keep >> r) & 1u) ? dpr * inv_keep : 0.f;
+          ds[r] = p[r] * (dpr - d4[i]) * scale;
+        }
       }
-      bf16x8_t df0 = dlayout_to_afrag(ds);
-      bf16x8_t df1 = dlayout_to_afrag(ds + 8);
+      const bf16x8_t df0 = dlayout_pack(ds);
+      const bf16x8_t df1 = dlayout_pack(ds + 8);
+      // dK += dS^T x Q
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
         bf16x8_t b0 = read_tr_frag(ldsQt, 32 * cb + (lane & 31), 16 * (lane >> 5));
@@ -882,16 +953,19 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   u16* base = (u16*)smem;               // [2][TILE] = K rm | V rm | Kt
-  u16* ldsDS = base + 2 * TILE;         // per wave + w*32*32 (bf16)
+  // dO fragments of this wave's strips, constant over the k loop: each lane
+  // parks its own SPW*NCH fragments here once and reads back only those, so
+  // no barrier guards them and a 16-byte read per lane is conflict-free.
+  bf16x8_t* ldsDOf = (bf16x8_t*)(base + 2 * TILE) + w * (SPW * NCH * 64) + lane;
 
   const u16* qg = q + (bh * T) * C;
   const u16* kg = k + (bh * T) * C;
   const u16* vg = v + bh_base(sv, bh, H);
   const u16* dog = dO + bh_base(sdo, bh, H);
 
-  // Under DROP at C=128 the keep mask does not fit beside 32 VGPRs of
-  // resident Q (the DROP=false kernel uses 255 of 256), so that variant
-  // re-reads Q from global (L2-resident) like the non-last strips do.
+  // Under DROP at C=128 that variant re-reads Q from global (L2-resident)
+  // like the non-last strips do. (Decided when the DROP=false kernel used
+  // 255 of 256 VGPRs; it uses 193 now, so resident Q may fit there too.)
   constexpr bool QF_RES = !(DROP && C == 128);
   bf16x8_t qf[QF_RES ? NCH : 1];  // registers only for the last (busiest) strip
   f32x16 dqacc[SPW][NCB];
@@ -905,6 +979,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(
       for (int ch = 0; ch < NCH; ++ch)
         qf[ch] = *(const bf16x8_t*)(qrow + 16 * ch + 8 * (lane >> 5));
     }
+    const u16* dorow = dog + myq * sdo.r;
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch)
+      ldsDOf[(sp * NCH + ch) * 64] = *(const bf16x8_t*)(dorow + 16 * ch + 8 * (lane >> 5));
     mylse[sp] = lse[bh * T + myq];
     mydelta[sp] = delta[bh * T + myq];
 #pragma unroll
@@ -917,11 +995,12 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(
     u16* bk = base + buf * TILE;
     stage_rm<C, NW * 64>(kg + k0 * C, bk);
     stage_rm<C, NW * 64>(vg + k0 * sv.r, bk + 32 * C, sv.r);
-    stage_tr<C, NW * 64>(kg + k0 * C, bk + 2 * 32 * C);
+    stage_tr<C, NW * 64, true>(kg + k0 * C, bk + 2 * 32 * C);
   };
   stage_set(0, 0);
   __syncthreads();
-  TrStage<C, NW * 64> kst;  // ONE load feeds K rm + Kt images
+  __builtin_amdgcn_s_waitcnt(0);  // as in the dkv kernel
+  TrStage<C, NW * 64, true> kst;  // ONE load feeds K rm + Kt images
   RmStage<C, NW * 64> vst;
   for (int kt = 0; kt < nkt; ++kt) {
     const int buf = kt & 1;
@@ -938,21 +1017,35 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(
     for (int sp = 0; sp < SPW; ++sp) {
       const int qw0 = q0 + 32 * strip[sp];
       if (k0 > qw0 + 31) continue;
-      const u16* qrow = qg + (long)(qw0 + (lane & 31)) * C;
-      const u16* dorow = dog + (long)(qw0 + (lane & 31)) * sdo.r;
-      // DROP: bit r = keep(q of reg r, kcol). Evaluated before the MFMA
-      // phase, while s/dp/ds are dead, and fenced so the Philox
-      // temporaries never overlap them (the kernel sits at the VGPR cap).
+      const int myq = qw0 + (lane & 31);
+      const u16* qrow = qg + (long)myq * C;
+      // DROP: bit r = keep(myq, k of reg r). The mask groups four
+      // consecutive q at one k into one Philox call; here registers run
+      // along k at ONE q, and the four lanes of a quad hold q = 4g..4g+3
+      // at the same 16 k (as in attn_fwd_kernel): quad lane j evaluates the
+      // calls of registers 4j..4j+3, and every lane picks its own q's bit
+      // out of the four quad masks. Evaluated before the MFMA phase, while
+      // s/dp/ds are dead, and fenced so the Philox temporaries never
+      // overlap them.
       uint32_t keep = 0;
       if constexpr (DROP) {
+        const int j = lane & 3;
+        uint32_t mine = 0;
 #pragma unroll
-        for (int g = 0; g < 4; ++g)
-          keep |= attn_drop_keep4(seed_lo, seed_hi, (uint32_t)bh,
-                                  (uint32_t)(qw0 + 8 * g + 4 * (lane >> 5)) >> 2,
-                                  (uint32_t)(k0 + (lane & 31)), drop_thr) << (4 * g);
+        for (int c = 0; c < 4; ++c)
+          mine |= attn_drop_keep4(seed_lo, seed_hi, (uint32_t)bh, (uint32_t)myq >> 2,
+                                  (uint32_t)(k0 + c + 8 * j + 4 * (lane >> 5)),
+                                  drop_thr) << (4 * c);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const uint32_t mg = (uint32_t)__shfl((int)mine, g, 4);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) keep |= ((mg >> (4 * c + j)) & 1u) << (4 * g + c);
+        }
         __builtin_amdgcn_sched_barrier(0);
       }
-      // S = Q x K^T and dP = dO x V^T in one pass.
+      // S^T = K x Q^T and dP^T = V x dO^T in one pass: the key in the
+      // registers (mfma_d_row), the query on the lane.
       f32x16 s = (f32x16)(0.f);
       f32x16 dp = (f32x16)(0.f);
 #pragma unroll
@@ -960,44 +1053,31 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(
         bf16x8_t kfrag = read_rm_frag<C>(ldsK, lane & 31, 16 * ch * 2 + 16 * (lane >> 5));
         bf16x8_t qfr = (QF_RES && sp == SPW - 1) ? qf[QF_RES ? ch : 0]
             : *(const bf16x8_t*)(qrow + 16 * ch + 8 * (lane >> 5));
-        s = mfma_32x32x16_bf16(qfr, kfrag, s);
+        s = mfma_32x32x16_bf16(kfrag, qfr, s);
         bf16x8_t vfrag = read_rm_frag<C>(ldsV, lane & 31, 16 * ch * 2 + 16 * (lane >> 5));
-        bf16x8_t dof = *(const bf16x8_t*)(dorow + 16 * ch + 8 * (lane >> 5));
-        dp = mfma_32x32x16_bf16(dof, vfrag, dp);
+        dp = mfma_32x32x16_bf16(vfrag, ldsDOf[(sp * NCH + ch) * 64], dp);
       }
-      // rows q are reg-mapped; cols k = lane&31. lse/delta per q via shfl.
+      // LSE and delta of this lane's q are its own scalars.
       float ds[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int qrow = qw0 + mfma_d_row(lane, r);
-        const float l_r = shfl32(mylse[sp], mfma_d_row(lane, r));
-        const float d_r = shfl32(mydelta[sp], mfma_d_row(lane, r));
-        const int kcol = k0 + (lane & 31);
-        float pv = (kcol > qrow) ? 0.f : __expf(s[r] * scale - l_r);
+        const int krow = k0 + mfma_d_row(lane, r);
+        float pv = (krow > myq) ? 0.f : __expf(s[r] * scale - mylse[sp]);
         float dpr = dp[r];
         if constexpr (DROP) dpr = ((keep >> r) & 1u) ? dpr * inv_keep : 0.f;
-        ds[r] = pv * (dpr - d_r) * scale;
+        ds[r] = pv * (dpr - mydelta[sp]) * scale;
       }
-      // transpose dS through per-wave LDS -> A-frags A[q = lane&31][k]
-      u16* dsl = ldsDS + w * 32 * 32;
+      // dQ += dS x K sums over dS^T's register (k) index: packed pairwise
+      // it is the A operand as it stands, against a Kt image whose k
+      // positions follow acc_k_pos.
+      const bf16x8_t a0 = dlayout_pack(ds), a1 = dlayout_pack(ds + 8);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = mfma_d_row(lane, r);  // q-local
-        *(u16*)((char*)(dsl + row * 32) + swz_tr(row, (lane & 31) * 2)) = f2b(ds[r]);
+      for (int cb = 0; cb < NCB; ++cb) {
+        bf16x8_t b0 = read_tr_frag(ldsKt, 32 * cb + (lane & 31), 16 * (lane >> 5));
+        bf16x8_t b1 = read_tr_frag(ldsKt, 32 * cb + (lane & 31), 32 + 16 * (lane >> 5));
+        dqacc[sp][cb] = mfma_32x32x16_bf16(a0, b0, dqacc[sp][cb]);
+        dqacc[sp][cb] = mfma_32x32x16_bf16(a1, b1, dqacc[sp][cb]);
       }
-      __builtin_amdgcn_s_waitcnt(0);
-#pragma unroll
-      for (int kc = 0; kc < 2; ++kc) {
-        bf16x8_t a = *(const bf16x8_t*)((const char*)(dsl + (lane & 31) * 32) +
-                                        swz_tr(lane & 31, (16 * kc + 8 * (lane >> 5)) * 2));
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-          bf16x8_t b = read_tr_frag(ldsKt, 32 * cb + (lane & 31),
-                                    (16 * kc + 8 * (lane >> 5)) * 2);
-          dqacc[sp][cb] = mfma_32x32x16_bf16(a, b, dqacc[sp][cb]);
-        }
-      }
-      __builtin_amdgcn_s_waitcnt(0);  // dsl reads done before next overwrite
     }
     if (pre) {
       u16* bk = base + (buf ^ 1) * TILE;

@@ -491,6 +491,21 @@ static void attn_fwd_launch(const AttnQK& a, const u16* vp, AttnStrides sv, u16*
   });
 }
 
+// delta = rowsum(dO * o) over N = B*H*T rows, visited in the memory order of
+// dO; do_copy != nullptr: dO is also written there as packed (B,H,T,C).
+static void attn_delta_launch(const AttnQK& a, const u16* dop, AttnStrides sdo, const u16* op,
+                              AttnStrides so, float* deltap, u16* do_copy) {
+  const long N = a.rows();
+  TORCH_CHECK(N < (1L << 31), "attn: B*H*T must be below 2^31");
+  dispatch_int<128, 64>(a.C, [&](auto c) {  // attn_qk admits these two only
+    constexpr int CC = decltype(c)::value;
+    constexpr long RPB = 4 * (64 / (CC / 8));  // rows per 4-wave block
+    const long dgrid = std::min((N + RPB - 1) / RPB, (long)8192);
+    launch(attn_delta_kernel<CC>, dgrid, 256, 0, dop, op, deltap, N, a.H, a.T, sdo, so,
+           do_copy, (int)(sdo.h < sdo.r));
+  });
+}
+
 // One backward launcher for every layout: dO, v, o are read and dv written
 // through strides. do_copy: see attn_bwd_packed. Returns {dq, dk} (B,H,T,C).
 static std::vector<torch::Tensor> attn_bwd_launch(
@@ -498,13 +513,9 @@ static std::vector<torch::Tensor> attn_bwd_launch(
     const u16* op, AttnStrides so, const float* lsep, u16* dvp, AttnStrides sdv,
     const MaybeDrop& drop, u16* do_copy = nullptr) {
   const int B = a.B, H = a.H, T = a.T, C = a.C;
-  const long N = a.rows();
-  TORCH_CHECK(N < (1L << 31), "attn: B*H*T must be below 2^31");
   auto delta = torch::empty({B, H, T}, a.opt.dtype(torch::kFloat));
   const float* deltap = fresh<float>(delta);
-  long dgrid = std::min((N + 3) / 4, (long)8192);
-  launch(attn_delta_kernel, dgrid, 256, 0, dop, op, fresh<float>(delta), N, C, H, T,
-         sdo, so, do_copy, (int)(sdo.h < sdo.r));
+  attn_delta_launch(a, dop, sdo, op, so, fresh<float>(delta), do_copy);
   if (do_copy) {  // the delta kernel left dO as packed (B,H,T,C) there
     dop = do_copy;
     sdo = strides_bhtc(H, T, C);
@@ -522,11 +533,19 @@ static std::vector<torch::Tensor> attn_bwd_launch(
     constexpr int CC = decltype(c)::value, NN = decltype(nw)::value;
     constexpr bool DROP = decltype(dr)::value;
     // double-buffered staging: dkv = 2x(Q,Qt,dO,dOt) + lse/delta;
-    // dq = 2x(K,V,Kt) + per-wave dS; both reused as [NW][32*32] fp32.
-    const size_t smem_dkv = std::max((size_t)(2 * 4 * 32 * CC) * 2 + 2 * 64 * 4,
-                                     (size_t)(NN * 32 * 32 * 4));
-    const size_t smem_dq = std::max((size_t)(2 * 3 * 32 * CC) * 2 + NN * 32 * 32 * 2,
-                                    (size_t)(NN * 32 * 32 * 4));
+    // dq = 2x(K,V,Kt); both reused as [NW][32*32] fp32. Behind it the
+    // resident fragments of the workgroup's own rows (V and a few of K in
+    // dkv, dO in dq): [NW][32][C] bf16 for each whole set. Sized so that no
+    // instantiation holds fewer workgroups per CU than its registers allow.
+    const size_t resident = (size_t)NN * 32 * CC * 2;
+    const size_t smem_dkv = (size_t)(2 * 4 * 32 * CC) * 2 + 2 * 64 * 4 +
+                            (attn_dkv_vf_lds<CC, NN> ? resident : 0) +
+                            (size_t)attn_dkv_kf_lds<CC, NN> * NN * 64 * 16;
+    static_assert((size_t)(2 * 4 * 32 * CC) * 2 >= (size_t)NN * 32 * 32 * 4,
+                  "epilogue bounce fits");
+    const size_t smem_dq = (size_t)(2 * 3 * 32 * CC) * 2 + resident;
+    static_assert((size_t)(2 * 3 * 32 * CC) * 2 + (size_t)NN * 32 * CC * 2 >=
+                  (size_t)NN * 32 * 32 * 4, "epilogue bounce fits");
     launch(attn_bwd_dkv_kernel<CC, NN, DROP>, grid, NN * 64, smem_dkv, dop, a.q, a.k, vp,
            lsep, deltap, fresh<u16>(dk), dvp, B, H, T, sdo, sv, sdv,
            d.seed_lo, d.seed_hi, d.thr, d.inv_keep);
@@ -634,6 +653,28 @@ std::vector<torch::Tensor> attn_bwd_packed(torch::Tensor dO, torch::Tensor q,
   if (stage_do) do_copy = torch::empty_like(q);
   return attn_bwd_launch(a, dop, so, vp, sv, op, so, lsep, dvp, sdv, drop_if(p, seed),
                          stage_do ? fresh<u16>(do_copy) : nullptr);
+}
+
+// The backward's first kernel on its own: delta (B,H,T) of dO and o, which
+// are both (B,H,T,C) or, with bthc, both (B,T,H,C); then the packed
+// (B,H,T,C) copy of dO that the kernel writes on the way is returned too.
+std::vector<torch::Tensor> attn_delta(torch::Tensor dO, torch::Tensor o, bool bthc) {
+  Call c("attn_delta", dO);
+  const u16* dop = c.bf16(dO, "dO", {ANY, ANY, ANY, ANY});
+  const u16* op = c.bf16(o, "o", dO.sizes());
+  const int d1 = c.dim(dO, 1), d2 = c.dim(dO, 2), C = c.dim(dO, 3);
+  const int H = bthc ? d2 : d1, T = bthc ? d1 : d2;
+  TORCH_CHECK(C == 64 || C == 128, "attn_delta: head dim 64 or 128 (got ", C, ")");
+  const AttnQK a{c.dim(dO, 0), H, T, C, nullptr, nullptr, dO.options()};
+  const AttnStrides st = bthc ? strides_bthc(H, T, C) : strides_bhtc(H, T, C);
+  auto delta = torch::empty({a.B, H, T}, dO.options().dtype(torch::kFloat));
+  if (!bthc) {
+    attn_delta_launch(a, dop, st, op, st, fresh<float>(delta), nullptr);
+    return {delta};
+  }
+  auto do_copy = torch::empty({a.B, H, T, C}, dO.options());
+  attn_delta_launch(a, dop, st, op, st, fresh<float>(delta), fresh<u16>(do_copy));
+  return {delta, do_copy};
 }
 
 // ---------------------------------------------------------------------------
@@ -1222,6 +1263,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("adamw_step", &adamw_step);
   mod.def("attn_fwd", &attn_fwd);
   mod.def("attn_bwd", &attn_bwd);
+  mod.def("attn_delta", &attn_delta, py::arg("dO"), py::arg("o"), py::arg("bthc"));
   mod.def("attn_fwd_dropout", &attn_fwd_dropout);
   mod.def("attn_bwd_dropout", &attn_bwd_dropout);
   mod.def("attn_fwd_packed", &attn_fwd_packed, py::arg("q"), py::arg("k"),

@@ -11,6 +11,7 @@ using u16 = unsigned short;
 using u16x2 = __attribute__((ext_vector_type(2))) unsigned short;
 using u16x4 = __attribute__((ext_vector_type(4))) unsigned short;
 using u16x8 = __attribute__((ext_vector_type(8))) unsigned short;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x8 = __attribute__((ext_vector_type(8))) float;

@@ -25,6 +25,31 @@ DEVINL unsigned pack_bf16(float lo, float hi) {
   return ((unsigned)f2b(hi) << 16) | (unsigned)f2b(lo);
 }
 
+// Position of row i (0..31) of a k axis in an image that an accumulator tile
+// reads as the other operand of its next MFMA: bits 2 and 3 exchanged (an
+// involution). Element j of lane half h of a 16-byte read at positions
+// 16s + 8h + j is then row 16s + 8(j>>2) + 4h + (j&3), which is what
+// dlayout_pack puts into element j of that half.
+DEVINL int acc_k_pos(int i) {
+  return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1);
+}
+
+// 8 f32 D-layout registers (regs 8s..8s+7 of a 32x32 accumulator X) packed
+// pairwise into the bf16x8 fragment of k-step s of a product that sums over
+// X's row index (X^T·B as the A operand, A·X as the B operand): no lane
+// movement. The k order inside the step is permuted, see acc_k_pos. keep8:
+// bit i clear zeroes s[i] (applied to the packed pairs).
+DEVINL bf16x8_t dlayout_pack(const float* s /*8 vals*/, unsigned keep8 = 0xffu) {
+  union { unsigned u[4]; bf16x8_t v; } out;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned mk = (((keep8 >> (2 * i)) & 1u) ? 0x0000ffffu : 0u) |
+                        (((keep8 >> (2 * i + 1)) & 1u) ? 0xffff0000u : 0u);
+    out.u[i] = pack_bf16(s[2 * i], s[2 * i + 1]) & mk;
+  }
+  return out.v;
+}
+
 // Convert 8 f32 D-layout registers (regs rb..rb+7 of a 32x32 accumulator,
 // holding rows {0..3, 8..11} + 4*(lane>>5) of some logical axis) into ONE
 // bf16x8 A-fragment covering rows 0..15 of that axis (k-chunk), using

@@ -65,25 +65,35 @@ DEVINL int swz_tr(int row, int byte_in_row) {
 template <int C, int NT>
 struct RmStage {
   static constexpr int NV = (32 * C + NT * 8 - 1) / (NT * 8);
+  // The first NF passes take every thread. Only a last, partial pass is
+  // predicated: a run-time exec branch around a load hides from the compiler
+  // which loads are outstanding, and the waits it then places for safety
+  // land in the tile loop's MFMA phase.
+  static constexpr int NF = (32 * C) / (NT * 8);
   u16x8 v[NV];
+  DEVINL void load1(const u16* __restrict__ g, int ld, unsigned boff, int i) {
+    v[i] = *(const u16x8*)((const char*)(g + (long)(i * (NT * 8 / C)) * ld) + boff);
+  }
   DEVINL void load(const u16* __restrict__ g, int ld = C) {
     static_assert((NT * 8) % C == 0, "a thread keeps its column across loads");
     const int idx0 = threadIdx.x * 8;
     const unsigned boff = 2u * (unsigned)((idx0 / C) * ld + idx0 % C);  // bytes
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      if (idx0 + i * NT * 8 < 32 * C)
-        v[i] = *(const u16x8*)((const char*)(g + (long)(i * (NT * 8 / C)) * ld) + boff);
+    for (int i = 0; i < NF; ++i) load1(g, ld, boff, i);
+    if constexpr (NV > NF) {
+      if (idx0 + NF * NT * 8 < 32 * C) load1(g, ld, boff, NF);
     }
+  }
+  DEVINL void write1(u16* lds, int i) const {
+    const int idx = threadIdx.x * 8 + i * NT * 8;
+    const int row = idx / C, col = idx % C;
+    *(u16x8*)((char*)lds + row * C * 2 + swz_rm<C>(row, col * 2)) = v[i];
   }
   DEVINL void write(u16* lds) const {
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int idx = threadIdx.x * 8 + i * NT * 8;
-      if (idx < 32 * C) {
-        const int row = idx / C, col = idx % C;
-        *(u16x8*)((char*)lds + row * C * 2 + swz_rm<C>(row, col * 2)) = v[i];
-      }
+    for (int i = 0; i < NF; ++i) write1(lds, i);
+    if constexpr (NV > NF) {
+      if ((int)threadIdx.x * 8 + NF * NT * 8 < 32 * C) write1(lds, NF);
     }
   }
 };
@@ -91,90 +101,93 @@ struct RmStage {
 // also the row-major image (both from ONE set of global loads).
 // ACCK (the backward kernels): the transposed image has its 32 rows at
 // acc_k_pos (mfma.h) inside each image row, for a reader whose other operand
-// is a dlayout_pack'ed accumulator, and both code paths below are the ones
-// that keep a tile loop's staging in registers from load to ds_write.
+// is a dlayout_pack'ed accumulator.
 template <int C, int NT, bool ACCK = false>
 struct TrStage {
   static constexpr int NP = (32 * C + NT * 16 - 1) / (NT * 16);
+  static constexpr int NF = (32 * C) / (NT * 16);  // unpredicated, as in RmStage
+  // Whether this thread has a part in pass i: known at compile time but for
+  // a last, partial pass.
+  static DEVINL bool mine(int i) { return (int)threadIdx.x * 16 + i * NT * 16 < 32 * C; }
   u16x8 a[NP], b[NP];  // rows 2p and 2p+1 at an 8-col span
+  DEVINL void load1(const u16* __restrict__ g, int ld, unsigned boff, int i) {
+    // row pair i of this thread: 2 * (NT * 8 / C) rows further down
+    const u16* gi = g + (long)(i * 2 * (NT * 8 / C)) * ld;
+    // Row 2p+1 sits one (wave-uniform, runtime) row stride after row 2p.
+    // Kept opaque so that the second address is formed from the first at
+    // issue time, not carried through the tile loop as a pointer of its own.
+    int ldb = 2 * ld;
+    asm volatile("" : "+s"(ldb));
+    if constexpr (ACCK) {
+      // Wave-uniform base plus a 32-bit lane offset, opaque so that the
+      // loop keeps no 64-bit per-lane pointer alive from tile to tile.
+      unsigned off = boff;
+      asm volatile("" : "+v"(off));
+      a[i] = *(const u16x8*)((const char*)gi + off);
+      b[i] = *(const u16x8*)((const char*)gi + ldb + off);
+    } else {
+      const char* pa = (const char*)gi + boff;
+      a[i] = *(const u16x8*)pa;
+      b[i] = *(const u16x8*)(pa + ldb);
+    }
+  }
   DEVINL void load(const u16* __restrict__ g, int ld = C) {
     static_assert((NT * 8) % C == 0, "a thread keeps its column across loads");
     const int idx0 = threadIdx.x * 16;
     const unsigned boff =  // bytes
         2u * (unsigned)(2 * (idx0 / (2 * C)) * ld + (idx0 / 2) % C);
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      if (idx0 + i * NT * 16 >= 32 * C) continue;
-      // row pair i of this thread: 2 * (NT * 8 / C) rows further down
-      const u16* gi = g + (long)(i * 2 * (NT * 8 / C)) * ld;
-      const char* pa = (const char*)gi + boff;
-      // Row 2p+1 sits one (wave-uniform, runtime) row stride after row 2p.
-      // Kept opaque so that the second address is formed from the first at
-      // issue time, not carried through the tile loop as a pointer of its own.
-      int ldb = 2 * ld;
-      asm volatile("" : "+s"(ldb));
-      if constexpr (ACCK) {
-        // Wave-uniform base plus a 32-bit lane offset, opaque so that the
-        // loop keeps no 64-bit per-lane pointer alive from tile to tile.
-        unsigned off = boff;
-        asm volatile("" : "+v"(off));
-        a[i] = *(const u16x8*)((const char*)gi + off);
-        b[i] = *(const u16x8*)((const char*)gi + ldb + off);
-        continue;
-      }
-      a[i] = *(const u16x8*)pa;
-      b[i] = *(const u16x8*)(pa + ldb);
+    for (int i = 0; i < NF; ++i) load1(g, ld, boff, i);
+    if constexpr (NP > NF) {
+      if (mine(NF)) load1(g, ld, boff, NF);
     }
   }
   // A row pair (2p, 2p+1) stays a pair under acc_k_pos.
+  DEVINL void write_tr1(u16* lds, int i) const {
+    const int idx = threadIdx.x * 16 + i * NT * 16;
+    const int row0 = 2 * (idx / (2 * C));
+    const int row = ACCK ? acc_k_pos(row0) : row0;
+    const int col = (idx / 2) % C;
+    // The pairs are cut out of the loaded dwords with integer ops.
+    // Element-wise u16 extraction (pv.x = a[i][j]; pv.y = b[i][j]) makes the
+    // compiler keep a and b in a stack slot: every tile's loads are then
+    // waited for and stored to scratch where they are issued, and the
+    // prefetch hides nothing.
+    const u32x4 aw = __builtin_bit_cast(u32x4, a[i]);
+    const u32x4 bw = __builtin_bit_cast(u32x4, b[i]);
+    // col is a multiple of 8, so swz_tr(col + j, x) is
+    // x ^ 32*((col>>3)&1) ^ 16*(j>>2): two bases per thread and the
+    // rest in the store's offset field, not eight address registers.
+    const int x = (row * 2) ^ (((col >> 3) & 1) << 5);
+    char* const p0 = (char*)lds + col * 64 + x;
+    char* const p1 = (char*)lds + col * 64 + (x ^ 16);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {  // LDS row = col + j
+      const unsigned pv = (j & 1)
+          ? (aw[j >> 1] >> 16) | (bw[j >> 1] & 0xffff0000u)
+          : (aw[j >> 1] & 0xffffu) | (bw[j >> 1] << 16);
+      *(unsigned*)((j < 4 ? p0 : p1) + j * 64) = pv;
+    }
+  }
   DEVINL void write_tr(u16* lds) const {
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int idx = threadIdx.x * 16 + i * NT * 16;
-      if (idx >= 32 * C) continue;
-      const int row0 = 2 * (idx / (2 * C));
-      const int row = ACCK ? acc_k_pos(row0) : row0;
-      const int col = (idx / 2) % C;
-      if constexpr (ACCK) {
-        // The pairs are cut out of the loaded dwords with integer ops.
-        // Element-wise u16 extraction (below) makes the compiler keep a and
-        // b in a stack slot: every tile's loads are then waited for and
-        // stored to scratch where they are issued, and the prefetch hides
-        // nothing.
-        const u32x4 aw = __builtin_bit_cast(u32x4, a[i]);
-        const u32x4 bw = __builtin_bit_cast(u32x4, b[i]);
-        // col is a multiple of 8, so swz_tr(col + j, x) is
-        // x ^ 32*((col>>3)&1) ^ 16*(j>>2): two bases per thread and the
-        // rest in the store's offset field, not eight address registers.
-        const int x = (row * 2) ^ (((col >> 3) & 1) << 5);
-        char* const p0 = (char*)lds + col * 64 + x;
-        char* const p1 = (char*)lds + col * 64 + (x ^ 16);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {  // LDS row = col + j
-          const unsigned pv = (j & 1)
-              ? (aw[j >> 1] >> 16) | (bw[j >> 1] & 0xffff0000u)
-              : (aw[j >> 1] & 0xffffu) | (bw[j >> 1] << 16);
-          *(unsigned*)((j < 4 ? p0 : p1) + j * 64) = pv;
-        }
-        continue;
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int r = col + j;  // LDS row = c
-        u16x2 pv; pv.x = a[i][j]; pv.y = b[i][j];
-        *(u16x2*)((char*)lds + r * 64 + swz_tr(r, row * 2)) = pv;
-      }
+    for (int i = 0; i < NF; ++i) write_tr1(lds, i);
+    if constexpr (NP > NF) {
+      if (mine(NF)) write_tr1(lds, NF);
     }
+  }
+  DEVINL void write_rm1(u16* lds, int i) const {
+    const int idx = threadIdx.x * 16 + i * NT * 16;
+    const int row = 2 * (idx / (2 * C));
+    const int col = (idx / 2) % C;
+    *(u16x8*)((char*)lds + row * C * 2 + swz_rm<C>(row, col * 2)) = a[i];
+    *(u16x8*)((char*)lds + (row + 1) * C * 2 + swz_rm<C>(row + 1, col * 2)) = b[i];
   }
   DEVINL void write_rm(u16* lds) const {
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int idx = threadIdx.x * 16 + i * NT * 16;
-      if (idx >= 32 * C) continue;
-      const int row = 2 * (idx / (2 * C));
-      const int col = (idx / 2) % C;
-      *(u16x8*)((char*)lds + row * C * 2 + swz_rm<C>(row, col * 2)) = a[i];
-      *(u16x8*)((char*)lds + (row + 1) * C * 2 + swz_rm<C>(row + 1, col * 2)) = b[i];
+    for (int i = 0; i < NF; ++i) write_rm1(lds, i);
+    if constexpr (NP > NF) {
+      if (mine(NF)) write_rm1(lds, NF);
     }
   }
 };
@@ -267,6 +280,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const u16* __restr
   stage_rm<C, NW * 64>(kg, ldsK);
   stage_tr<C, NW * 64>(vg, ldsVt, sv.r);
   __syncthreads();
+  // Every prologue load (Q fragments, staging) has landed, as in the backward
+  // kernels: the vmcnt waits inside the loop then count its own prefetch alone
+  // and stand in front of the staged tile's ds_write, not among the S MFMAs.
+  __builtin_amdgcn_s_waitcnt(0);
 
   RmStage<C, NW * 64> kst;
   TrStage<C, NW * 64> vst;
@@ -423,7 +440,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
   constexpr int NCH = C / 16;
   const float scale = rsqrtf((float)C);
   const long bh = blockIdx.x % ((long)B * H);
-  const int qb = blockIdx.x / (B * H);
+  // The last q-block has the most rounds: heaviest first, so that the grid's
+  // tail is made of the short blocks (-1.4 % per call at T=1024; the same
+  // order measured +1.0 % in the dq kernel, which keeps the ascending one).
+  const int qb = T / (NW * 32) - 1 - blockIdx.x / (B * H);
   const int q0 = qb * (NW * 32);
   const int lane = lane_id();
   const int w = wave_id();
@@ -458,6 +478,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd2_kernel(
   stage_tr<C, NW * 64>(vg, ldsVt, sv.r);
   stage_tr<C, NW * 64>(vg + (long)32 * sv.r, ldsVt + C * 32, sv.r);
   __syncthreads();
+  __builtin_amdgcn_s_waitcnt(0);  // as in attn_fwd_kernel
 
   RmStage<C, NW * 64> kstA, kstB;
   TrStage<C, NW * 64> vstA, vstB;
@@ -703,8 +724,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
   const u16* vg = v + bh_base(sv, bh, H);
   const u16* dog = dO + bh_base(sdo, bh, H);
   const u16* krow = kg + (long)myk * C;
-  const u16* vrow = vg + (long)myk * sv.r;
+  const unsigned vrow_off = 2u * (unsigned)(myk * sv.r + 8 * (lane >> 5));  // bytes
   if constexpr (VF_LDS) {
+    const u16* vrow = vg + (long)myk * sv.r;
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch)
       ldsVf[ch * 64] = *(const bf16x8_t*)(vrow + 16 * ch + 8 * (lane >> 5));
@@ -825,8 +847,15 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
       // dV += P^T x dO. P^T x B sums over P's register (q) index: packed
       // pairwise P is the A operand as it stands, against a dOt image whose
       // q positions follow acc_k_pos. The same holds for dS and Qt below.
-      const bf16x8_t pf0 = dlayout_pack(p, DROP ? keep : 0xffu);
-      const bf16x8_t pf1 = dlayout_pack(p + 8, DROP ? keep >> 8 : 0xffu);
+      bf16x8_t pf0 = dlayout_pack(p, DROP ? keep : 0xffu);
+      bf16x8_t pf1 = dlayout_pack(p + 8, DROP ? keep >> 8 : 0xffu);
+      // Formed here, and the phases kept in this order: the pack is a few
+      // pure instructions that would otherwise be placed behind the dP
+      // phase with all dOt fragments read ahead of it, and at C=128 the
+      // resident K fragments then spill into the loop (a sched_barrier
+      // alone does not hold a pure value). Likewise for dS below.
+      asm volatile("" : "+v"(pf0), "+v"(pf1));
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
         bf16x8_t b0 = read_tr_frag(ldsDOt, 32 * cb + (lane & 31), 16 * (lane >> 5));
@@ -840,8 +869,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
       for (int ch = 0; ch < NCH; ++ch) {
         bf16x8_t a = read_rm_frag<C>(ldsDO, lane & 31, 16 * ch * 2 + 16 * (lane >> 5));
         bf16x8_t vf;
-        if constexpr (VF_LDS) vf = ldsVf[ch * 64];
-        else vf = *(const bf16x8_t*)(vrow + 16 * ch + 8 * (lane >> 5));
+        if constexpr (VF_LDS) {
+          vf = ldsVf[ch * 64];
+        } else {
+          // wave-uniform base plus a 32-bit lane offset, as in TrStage::load
+          unsigned off = vrow_off;
+          asm volatile("" : "+v"(off));
+          vf = *(const bf16x8_t*)((const char*)vg + off + 32 * ch);
+        }
         dp = mfma_32x32x16_bf16(a, vf, dp);
       }
       // dS = P * (dP - delta[q]) * scale
@@ -857,8 +892,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(
           ds[r] = p[r] * (dpr - d4[i]) * scale;
         }
       }
-      const bf16x8_t df0 = dlayout_pack(ds);
-      const bf16x8_t df1 = dlayout_pack(ds + 8);
+      bf16x8_t df0 = dlayout_pack(ds);
+      bf16x8_t df1 = dlayout_pack(ds + 8);
+      asm volatile("" : "+v"(df0), "+v"(df1));
+      __builtin_amdgcn_sched_barrier(0);
       // dK += dS^T x Q
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {

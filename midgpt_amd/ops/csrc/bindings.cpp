@@ -120,6 +120,9 @@ struct Call {
   const long* i64(const torch::Tensor& t, const char* n, const Shape& s) const {
     return ptr<long, torch::kLong>(t, n, s);
   }
+  long* i64_out(const torch::Tensor& t, const char* n, const Shape& s) const {
+    return ptr<long, torch::kLong>(t, n, s);
+  }
   const int* i32(const torch::Tensor& t, const char* n, const Shape& s) const {
     return ptr<int, torch::kInt>(t, n, s);
   }
@@ -1246,6 +1249,18 @@ torch::Tensor probe_pack(torch::Tensor M, torch::Tensor B) {
   launch(probe_pack_kernel, 1, 64, 0, mp, bp, fresh<float>(D));
   return D;
 }
+// pack_bf16 against f2b over the n fp32 bit patterns from start on; the three
+// counts (probe.hip) are added into `counts`, int64 of 3 on the GPU.
+void probe_bf16_pack(torch::Tensor counts, int64_t start, int64_t n) {
+  Call c("probe_bf16_pack", counts);
+  long* cp = c.i64_out(counts, "counts", {3});
+  TORCH_CHECK(start >= 0 && start <= (int64_t)UINT32_MAX && n >= 0 && n <= (1LL << 32),
+              "probe_bf16_pack: start in [0, 2^32) and n in [0, 2^32] required, got ", start,
+              " and ", n);
+  const long grid = std::min((long)((n + 255) / 256), 4096L);
+  launch(probe_bf16_pack_kernel, grid, 256, 0, (uint32_t)start, (unsigned long long)n,
+         reinterpret_cast<unsigned long long*>(cp));
+}
 
 #include "blaslt.inc"
 
@@ -1317,4 +1332,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("matmul_dgelu", &matmul_dgelu);
   mod.def("probe_mfma", &probe_mfma);
   mod.def("probe_pack", &probe_pack);
+  mod.def("probe_bf16_pack", &probe_bf16_pack);
 }

@@ -20,9 +20,13 @@ DEVINL int mfma_d_row(int lane, int r) {
   return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
 }
 
-// pack two f32 into one dword of two bf16 (lo = first)
+// pack two f32 into one dword of two bf16 (lo = first): the vector conversion
+// compiles to one v_cvt_pk_bf16_f32. Bit for bit f2b for every input that is
+// not a NaN, and a NaN for every NaN (probe_bf16_pack sweeps all 2^32).
+using bf16x2_t = __attribute__((ext_vector_type(2))) __bf16;
 DEVINL unsigned pack_bf16(float lo, float hi) {
-  return ((unsigned)f2b(hi) << 16) | (unsigned)f2b(lo);
+  const f32x2 v = {lo, hi};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
 }
 
 // Position of row i (0..31) of a k axis in an image that an accumulator tile
